@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- the headline benchmark: joined tuples/s on the 4-relation chain join (config C3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--no-cpu] [--workload c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--workload c3|c4|c5]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-faithful] [--no-materialised]]
+
+A plain run sets up, warms up, times the K steps (no HIP events in the loop), writes the last
+step's outputs with `--dump-outputs` (benchmarks/dump.py) and prints the result line.  Everything
+else described below -- the stage table and `roofline`, the faithful executor's parity run and
+timing, the other plan forms, `cpu_baseline` -- is measured in runs of its own and only with `--full`.
 
 Workload (BASELINE.json configs[2]): four relations of R = 100 M rows
 (c0 = v % R, c1 = v % R, c2 = v >> 32, splitmix64 seed 1, generated straight into HBM), query
@@ -16,15 +22,15 @@ output is the relational answer, so it runs as a relat
 filters on rowid slices, joins reordered smallest-first, each join a sort-merge on its key buckets
 (qe_join_pairs), derived join sides exchanged by key over RCCL at N > 1 (grouped
 ncclSend/ncclRecv on the communicator's stream), sums all-reduced -- and prints the reference's
-bytes.  At N = 1 the faithful executor (qe_run_queries: the reference's state machine restated,
-every mid_result list kept) is timed in the same run and reported as `faithful_executor`
+bytes.  With `--full` at N = 1 the faithful executor (qe_run_queries: the reference's state machine
+restated, every mid_result list kept) is timed in the same run and reported as `faithful_executor`
 (`--plan faithful` makes it the measured line).
 `--scaling strong` (default, the north star's shape): 100 M rows per relation in total, whatever N;
-`--scaling weak`: 100 M rows per relation per GPU.  Rank 0 checks the printed bytes in-run against
-the faithful executor on the same relations (and, for the default workload, against the C3 output
-pinned by tests/test_gpu_fullsize.py::test_c3_chain_100m) and reports `parity`.
+`--scaling weak`: 100 M rows per relation per GPU.  Rank 0 checks the printed bytes against the C3
+output pinned by tests/test_gpu_fullsize.py::test_c3_chain_100m (default workload) and, with
+`--full`, in-run against the faithful executor on the same relations, and reports `parity`.
 
-The JSON line also carries `roofline` (the dominant kernel's algorithmic GB/s from HIP events on
+With `--full` the JSON line also carries `roofline` (the dominant kernel's algorithmic GB/s from HIP events on
 the libqe stream, against the 8 TB/s HBM3E peak) and `cpu_baseline` (oracle/cpu_ref, the C
 restatement of the reference path, single-threaded on a bounded sample of the same workload).
 """
@@ -40,6 +46,8 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "query-compiler-executor_amd"))
 sys.path.insert(0, ROOT)
+
+from benchmarks.dump import dump_outputs  # noqa: E402
 
 METRIC = "joined tuples/sec + achieved HBM GB/s, 4-rel chain join, 1/2/4/8 MI355X"
 # C3 at 100 M rows/relation, seed 1: the bytes tests/test_gpu_fullsize.py::test_c3_chain_100m pins
@@ -225,31 +233,37 @@ def run_dist(args):
             d = float(t.item())
         return d, o, rc_, rf
 
-    # 1) the stage table: every launch between two HIP events (their host cost stretches the
-    #    wall time, so this loop is not the one `value` comes from)
-    ctx.set_profiling(True)
-    ctx.reset_stats()
-    dt_stages, _, _, _ = timed_steps()
-    stage_stats = ctx.kernel_stats()
-    ctx.set_profiling(False)
-    # QE_RT_SITES=1: the host round trips by call site (zero-time stages "rt@file:line")
-    rt_sites = {k[3:]: stage_stats.pop(k)["launches"] / args.steps for k in
-                [k for k in stage_stats if k.startswith("rt@")]}
-    dominant = max(((k, v) for k, v in stage_stats.items() if v["ms"] > 0), key=lambda kv: kv[1]["ms"])[0]
-    # 2) the timed region: HIP events around the dominant kernel's launches only (its roofline)
-    ctx.set_profiling_only(dominant)
-    ctx.set_profiling(True)
-    ctx.reset_stats()
+    stage_stats, stats, rt_sites, dominant, dt_stages = {}, {}, {}, None, None
+    if args.full:
+        # 1) the stage table: every launch between two HIP events (their host cost stretches the
+        #    wall time, so this loop is not the one `value` comes from)
+        ctx.set_profiling(True)
+        ctx.reset_stats()
+        dt_stages, _, _, _ = timed_steps()
+        stage_stats = ctx.kernel_stats()
+        ctx.set_profiling(False)
+        # QE_RT_SITES=1: the host round trips by call site (zero-time stages "rt@file:line")
+        rt_sites = {k[3:]: stage_stats.pop(k)["launches"] / args.steps for k in
+                    [k for k in stage_stats if k.startswith("rt@")]}
+        dominant = max(((k, v) for k, v in stage_stats.items() if v["ms"] > 0), key=lambda kv: kv[1]["ms"])[0]
+        # 2) the timed region: HIP events around the dominant kernel's launches only (its roofline)
+        ctx.set_profiling_only(dominant)
+        ctx.set_profiling(True)
+        ctx.reset_stats()
+    # the timed region (a plain run: this loop alone, no HIP events in it)
     dt, out, rc, refused = timed_steps()
-    stats = ctx.kernel_stats()
-    ctx.set_profiling(False)
-    ctx.set_profiling_only(None)
+    if args.full:
+        stats = ctx.kernel_stats()
+        ctx.set_profiling(False)
+        ctx.set_profiling_only(None)
     rows = ctx.last_result_rows()
     exchanges, sent = comm.stats() if comm else (0, 0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rows)
     res = None
     faithful_line = None
     faithful = None
-    if rank == 0 and not args.no_faithful:
+    if rank == 0 and args.full and not args.no_faithful:
         faithful, _ = ctx.run(QUERY)              # in-run parity: the drop-in executor, same relations
     # 3) the same plan with the query's last join materialised (QE_PLAN_AGG=0: its pairs made by the
     #    chain bucket join, then summed by the checksum gathers) -- the line's own last join counts
@@ -270,7 +284,7 @@ def run_dist(args):
                 os.environ[var] = old
 
     mat_line = side_line = None
-    if not args.no_materialised and not args.no_faithful:   # (profiling runs: the measured plan only)
+    if args.full and not args.no_materialised and not args.no_faithful:   # (profiling runs: the measured plan only)
         dtm, out_m, _, _ = timed_with("QE_PLAN_AGG", "0")
         mat_line = {"last_join": "materialised: every result pair written (rowid pairs + carried columns), "
                                  "then the checksums gather the select columns",
@@ -300,8 +314,6 @@ def run_dist(args):
                              "ms_per_step": round(dtf / args.steps * 1e3, 3),
                              "value": round(ctx.last_result_rows() * args.steps / dtf, 1),
                              "stdout_identical": faithful == out}
-        kern = sorted(stage_stats.items(), key=lambda kv: -kv[1]["ms"])
-        traffic = load_traffic("c3_plan")
         res = {
             "metric": METRIC, "value": round(rows * args.steps / dt, 1), "unit": "joined tuples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -321,6 +333,11 @@ def run_dist(args):
                        "last_join": "aggregate (the last join's pairs counted, not materialised: only "
                                     "print_sums reads them; see materialised_last_join)",
                        "load_partition_s": round(t_part, 4) if t_part is not None else None},
+        }
+    if rank == 0 and args.full:
+        kern = sorted(stage_stats.items(), key=lambda kv: -kv[1]["ms"])
+        traffic = load_traffic("c3_plan")
+        res.update({
             "materialised_last_join": mat_line,
             "two_stream_sorts": side_line,
             "faithful_executor": faithful_line,
@@ -336,7 +353,7 @@ def run_dist(args):
             # of the stage-table loop), with its PMC traffic ratio where profiles/ has one
             "stage_roofline": stage_roofline(stage_stats, traffic, args.steps),
             "pmc_source": traffic.get("_file") if traffic else None,
-        }
+        })
         if not args.no_cpu and not multi:   # (rank 0 at N = 1 only: the baseline is per host, not per rank)
             res["cpu_baseline"] = cpu_baseline(args.cpu_rows, args.seed, ctx)
         else:
@@ -366,8 +383,9 @@ def run_single(args):
     for i in range(args.warmup):
         out, _ = ctx.run(QUERY)
         log(f"[bench] warmup {i}: {out.strip()!r}")
-    ctx.set_profiling(True)
-    ctx.reset_stats()
+    if args.full:                 # the stage table: HIP events around every launch of the timed loop
+        ctx.set_profiling(True)
+        ctx.reset_stats()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -375,11 +393,28 @@ def run_single(args):
     ctx.sync()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    stats = ctx.kernel_stats()
+    stats = ctx.kernel_stats() if args.full else {}
     ctx.set_profiling(False)
     rows = ctx.last_result_rows()
     ms = dt / args.steps * 1e3
     value = rows * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rows)
+    res = {
+        "metric": METRIC, "value": round(value, 1), "unit": "joined tuples/s", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
+        "scaling": args.scaling, "vs_baseline": None, "dtype": "u64",
+        "data": "synthetic: splitmix64 relations generated in HBM (SURVEY.md §9.1), seed %d" % args.seed,
+        "parity": pinned_parity(args, out),
+        "config": {"workload": "C3: 4-relation chain join R0-R1-R2-R3, 2 filters on R3, %d rows/rel" % args.rows,
+                   "query": QUERY.strip(), "rows_per_relation": args.rows, "result_rows": rows,
+                   "stdout": out, "executor": "libqe faithful state machine (qe_run_queries)",
+                   "dead_list_elimination": os.environ.get("QE_DLE", "1") != "0",
+                   "parallelism": "single GPU"},
+    }
+    if not args.full:
+        ctx.close()
+        return res
     # the same query with every intermediate rowid list materialised (QE_DLE=0), for the record
     dle_env = os.environ.get("QE_DLE")
     os.environ["QE_DLE"] = "0"
@@ -396,17 +431,7 @@ def run_single(args):
         os.environ["QE_DLE"] = dle_env
     kern = sorted(stats.items(), key=lambda kv: -kv[1]["ms"])
     total_kernel_ms = sum(s["ms"] for _, s in kern) / args.steps
-    res = {
-        "metric": METRIC, "value": round(value, 1), "unit": "joined tuples/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
-        "scaling": args.scaling, "vs_baseline": None, "dtype": "u64",
-        "data": "synthetic: splitmix64 relations generated in HBM (SURVEY.md §9.1), seed %d" % args.seed,
-        "parity": pinned_parity(args, out),
-        "config": {"workload": "C3: 4-relation chain join R0-R1-R2-R3, 2 filters on R3, %d rows/rel" % args.rows,
-                   "query": QUERY.strip(), "rows_per_relation": args.rows, "result_rows": rows,
-                   "stdout": out, "executor": "libqe faithful state machine (qe_run_queries)",
-                   "dead_list_elimination": os.environ.get("QE_DLE", "1") != "0",
-                   "parallelism": "single GPU"},
+    res.update({
         "all_lists_materialised": {"ms_per_step": round(dt_all / args.steps * 1e3, 3),
                                    "value": round(rows * args.steps / dt_all, 1),
                                    "stdout_identical": out_all == out},
@@ -415,7 +440,7 @@ def run_single(args):
         "stages": {k: {"ms_per_step": round(s["ms"] / args.steps, 3), "launches_per_step": s["launches"] / args.steps,
                        "GBps": round(s["alg_bytes"] / (s["ms"] * 1e-3) / 1e9, 1) if s["ms"] > 0 else None}
                    for k, s in kern[:12]},
-    }
+    })
     if not args.no_cpu:
         ctx.drop_relations()
         res["cpu_baseline"] = cpu_baseline(args.cpu_rows, args.seed, ctx)
@@ -540,6 +565,13 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--cpu-rows", type=int, default=16_000_000)
     ap.add_argument("--cpu-rows-c5", type=int, default=1_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the HIP-event stage table and the dominant stage's roofline, "
+                         "the other executors and plan forms timed on the same data, the in-run parity "
+                         "against the faithful executor and the CPU baseline (a plain run has none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/*.npy "
+                         "(benchmarks/dump.py)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-faithful", action="store_true",
                     help="skip the faithful executor's parity run and timing and the materialised-last-join "

@@ -20,6 +20,7 @@ import time
 from qe import datagen as dg
 
 from .cpuref import CpuRef, cpu_model, pin_one_core
+from .dump import dump_outputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "c4.json")
@@ -114,7 +115,8 @@ def run_single(args, log, roofline_fn=None, traffic_fn=None) -> dict:
     #    the wait).  Their host cost stretches a batch by ~16 % (r06u: 225 vs 189 ms), so this loop
     #    is not the one `value` comes from.
     stage_stats, dt_stages = {}, None
-    if events:
+    full = getattr(args, "full", False)          # a plain run: the timed batches alone
+    if events and full:
         ctx.set_profiling(True)
         ctx.reset_stats()
         dt_stages, _, _ = timed_batches()
@@ -134,6 +136,31 @@ def run_single(args, log, roofline_fn=None, traffic_fn=None) -> dict:
     ctx.set_profiling(False)
     ctx.set_profiling_only(None)
     hits1, builds1 = ctx.sort_cache_stats()
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, out, out.count("\n"))
+    res = {
+        "metric": METRIC, "value": round(len(queries) * args.steps / dt, 2), "unit": "queries/s", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64",
+        "data": "synthetic: qe.datagen.c4_spec(1.0) relations generated in HBM (seed 4)",
+        "parity": out == "".join(c["stdout"] for c in json.load(open(GOLDEN_FULL))["cases"])
+                  if os.path.exists(GOLDEN_FULL) else None,
+        "config": {"workload": "C4: 14 relations, %d gated SIGMOD-style queries in batches of %d"
+                               % (len(queries), dg.C4_BATCH),
+                   "rows_total": sum(s.rows for s in specs), "output_lines": out.count("\n"),
+                   "executor": "qe_run_queries_lanes: %s, %d concurrent lanes (worker contexts = HIP "
+                               "streams on this GPU, relations shared), output in input order"
+                               % ("the partitioned plan per query, faithful fallback" if plan
+                                  else "the faithful executor", workers),
+                   "parallelism": "single GPU, inter-query concurrency x%d" % workers},
+        "sort_cache": {"base_column_sorts_reused_per_step": (hits1 - hits0) / args.steps,
+                       "built_per_step": (builds1 - builds0) / args.steps,
+                       "scope": "one batch (qe_sort_cache brackets each qe_run_queries_lanes call): every step "
+                                "sorts each base column it joins at least once"},
+    }
+    if not full:
+        ctx.close()
+        return res
     kern = sorted(((k, v) for k, v in stage_stats.items() if not k.startswith("rt@")), key=lambda kv: -kv[1]["ms"])
 
     def timed(fn):
@@ -155,25 +182,7 @@ def run_single(args, log, roofline_fn=None, traffic_fn=None) -> dict:
               "partitioned_plan_one_lane (qe_run_queries_dist)": timed(lambda: ctx.run_dist(text)[0]),
               "faithful_lanes (qe_run_queries_parallel, %d lanes)" % workers:
                   timed(lambda: ctx.run_lanes(text, workers, plan=False)[0])}
-    res = {
-        "metric": METRIC, "value": round(len(queries) * args.steps / dt, 2), "unit": "queries/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64",
-        "data": "synthetic: qe.datagen.c4_spec(1.0) relations generated in HBM (seed 4)",
-        "parity": out == "".join(c["stdout"] for c in json.load(open(GOLDEN_FULL))["cases"])
-                  if os.path.exists(GOLDEN_FULL) else None,
-        "config": {"workload": "C4: 14 relations, %d gated SIGMOD-style queries in batches of %d"
-                               % (len(queries), dg.C4_BATCH),
-                   "rows_total": sum(s.rows for s in specs), "output_lines": out.count("\n"),
-                   "executor": "qe_run_queries_lanes: %s, %d concurrent lanes (worker contexts = HIP "
-                               "streams on this GPU, relations shared), output in input order"
-                               % ("the partitioned plan per query, faithful fallback" if plan
-                                  else "the faithful executor", workers),
-                   "parallelism": "single GPU, inter-query concurrency x%d" % workers},
-        "sort_cache": {"base_column_sorts_reused_per_step": (hits1 - hits0) / args.steps,
-                       "built_per_step": (builds1 - builds0) / args.steps,
-                       "scope": "one batch (qe_sort_cache brackets each qe_run_queries_lanes call): every step "
-                                "sorts each base column it joins at least once"},
+    res.update({
         "other_executors_same_batch": others,
         "roofline": roofline_fn(stats, traffic_fn() if traffic_fn else None) if roofline_fn else None,
         # (every lane's launches summed: lane time, ~3 kernels in flight at once)
@@ -188,7 +197,7 @@ def run_single(args, log, roofline_fn=None, traffic_fn=None) -> dict:
                if any(k.startswith("rt@") for k in stage_stats) else {}),
             "note": "the stage table's own loop (HIP events around every launch on every lane); value's loop times "
                     "only the dominant stage"},
-    }
+    })
     if not args.no_cpu:
         res["cpu_baseline"] = cpu_sample(queries, ctx)
     ctx.close()
@@ -244,6 +253,8 @@ def run_dist(args, log) -> dict | None:
         if r:
             rc = r
             break
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, text, text.count("\n"))
     want = "".join(c["stdout"] for c in json.load(open(GOLDEN_FULL))["cases"]) if os.path.exists(GOLDEN_FULL) else None
     return {
         "metric": METRIC, "value": round(len(queries) * args.steps / dt, 2), "unit": "queries/s", "n_gpus": world,

@@ -23,6 +23,7 @@ import time
 from qe import datagen as dg
 
 from .cpuref import CpuRef, cpu_model, pin_one_core
+from .dump import dump_outputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 METRIC = "input rows/sec, C5 2-relation Zipf(0.9) join, 1e9 rows/side (pairs counted, not materialised)"
@@ -101,8 +102,9 @@ def run_single(args, log, roofline_fn=None, traffic_fn=None) -> dict:
     out = None
     for _ in range(args.warmup):
         out, rc, _ = ctx.run_dist(dg.C5_QUERY)
-    ctx.set_profiling(True)
-    ctx.reset_stats()
+    if args.full:                 # the stage table: HIP events around every launch of the timed loop
+        ctx.set_profiling(True)
+        ctx.reset_stats()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -111,8 +113,10 @@ def run_single(args, log, roofline_fn=None, traffic_fn=None) -> dict:
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pairs = ctx.last_result_rows()
-    stats = ctx.kernel_stats()
+    stats = ctx.kernel_stats() if args.full else {}
     ctx.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, pairs)
     kern = sorted(stats.items(), key=lambda kv: -kv[1]["ms"])
     ms = dt / args.steps * 1e3
     res = {
@@ -131,10 +135,15 @@ def run_single(args, log, roofline_fn=None, traffic_fn=None) -> dict:
                    "path": PATH_ONE_RANK, "refused": refused,
                    "pairs_counted_per_s": round(pairs * args.steps / dt, 1),
                    "stdout": out, "parallelism": "single GPU"},
+    }
+    if not args.full:
+        ctx.close()
+        return res
+    res.update({
         "roofline": roofline_fn(stats, traffic_fn() if traffic_fn else None) if roofline_fn else None,
         "stages": {k: {"ms_per_step": round(s["ms"] / args.steps, 3), "launches_per_step": s["launches"] / args.steps}
                    for k, s in kern[:10]},
-    }
+    })
     if not args.no_cpu:
         res["cpu_baseline"] = cpu_sample(ctx, args.cpu_rows_c5)
     else:
@@ -179,8 +188,9 @@ def run_dist(args, log) -> dict | None:
     out = None
     for _ in range(args.warmup):
         out, rc, refused = ctx.run_dist(q, comm)
-    ctx.set_profiling(True)
-    ctx.reset_stats()
+    if args.full:                 # the stage table: HIP events around every launch of the timed loop
+        ctx.set_profiling(True)
+        ctx.reset_stats()
     if not solo:
         dist.barrier()
     torch.cuda.synchronize()
@@ -197,10 +207,12 @@ def run_dist(args, log) -> dict | None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     pairs = ctx.last_result_rows()
-    stats = ctx.kernel_stats()
+    stats = ctx.kernel_stats() if args.full else {}
     ctx.set_profiling(False)
     res = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, pairs)
         kern = sorted(stats.items(), key=lambda kv: -kv[1]["ms"])
         res = {
             "metric": METRIC, "value": round(2 * rows * args.steps / dt, 1), "unit": "input rows/s",
@@ -217,7 +229,8 @@ def run_dist(args, log) -> dict | None:
                        "pairs_counted_per_s": round(pairs * args.steps / dt, 1),
                        "stdout": out,
                        "parallelism": f"hash buckets + heavy split x{world}" if world > 1 else "single GPU"},
-            "stages": {k: {"ms_per_step": round(s["ms"] / args.steps, 3)} for k, s in kern[:10]},
+            **({"stages": {k: {"ms_per_step": round(s["ms"] / args.steps, 3)} for k, s in kern[:10]}}
+               if args.full else {}),
             "cpu_baseline": None,
         }
     if comm is not None:

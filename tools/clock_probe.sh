@@ -13,7 +13,7 @@ SMI=$!
 trap 'kill $SMI 2>/dev/null' EXIT
 for rep in 1 2; do
   echo "== run $rep start $(date +%s.%N | cut -c1-14)" >> $O
-  timeout -k 10 240 python bench.py --no-cpu --no-faithful --steps $S --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stages']; print('RESULT', d['ms_per_step'], d['kernel_ms_per_step'], d['roofline']['frac'], {k: v['ms_per_step'] for k, v in list(s.items())[:4]})" >> $O 2>&1 || exit 1
+  timeout -k 10 240 python bench.py --full --no-cpu --no-faithful --steps $S --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stages']; print('RESULT', d['ms_per_step'], d['kernel_ms_per_step'], d['roofline']['frac'], {k: v['ms_per_step'] for k, v in list(s.items())[:4]})" >> $O 2>&1 || exit 1
   echo "== run $rep end $(date +%s.%N | cut -c1-14)" >> $O
 done
 echo all-done

@@ -7,6 +7,6 @@ T=$1; shift
 ( for rep in 1 2; do for spec in "$@"; do
     label=${spec%%:*}; envs=${spec#*:}
     echo "== $label"
-    env $envs timeout -k 10 300 python bench.py --workload c4 --no-cpu --steps 3 --warmup 1 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['parity'], {k: v['ms_per_step'] for k, v in list(d['stages_lane0'].items())[:8]})" || exit 1
+    env $envs timeout -k 10 300 python bench.py --workload c4 --full --no-cpu --steps 3 --warmup 1 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['parity'], {k: v['ms_per_step'] for k, v in list(d['stages_lane0'].items())[:8]})" || exit 1
   done; done ) > gpurun_out/${T}_c4.log 2>&1
 rc=$?; echo c4ab rc=$rc; exit $rc

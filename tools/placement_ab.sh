@@ -9,7 +9,7 @@ O=$R/gpurun_out
 mkdir -p $O
 L=$O/${T}_placement.log
 : > $L
-A="--no-cpu --no-faithful --steps 10 --warmup 2"
+A="--full --no-cpu --no-faithful --steps 10 --warmup 2"
 summ() {   # the bench line's stage table (last JSON line of $1)
   python3 -c "
 import json,sys

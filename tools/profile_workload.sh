@@ -9,7 +9,7 @@ R=$(pwd)
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-A="--workload $W --steps 2 --warmup 1 --no-cpu $PROFILE_EXTRA"
+A="--workload $W --steps 2 --warmup 1 --full --no-cpu $PROFILE_EXTRA"
 # C4: a crash under the profiler leaves the fault address, PC and /proc/self/maps here (tools/crashmaps.c).
 # Under the profiler C4 runs ONE lane (QE_WORKERS=1): with eight lanes submitting at once the
 # profiler's HSA queue interception has faulted past its own 1 MiB buffer (in the trace
