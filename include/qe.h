@@ -136,6 +136,10 @@ int  qe_run_queries_parallel(qe_ctx*, int workers, const char* text, char** out,
  * qe_run_queries_dist's bytes).  workers <= 1 runs the batch on this ctx. */
 #define QE_EXEC_FAITHFUL 0
 #define QE_EXEC_PLAN 1
+/* QE_EXEC_RELATIONAL: each query through the plan's relational mode (qe_run_queries_relational
+ * below) on its lane's ctx as one rank -- the textbook answer, no fallback; the first failing query
+ * ends the batch with the output of the queries before it */
+#define QE_EXEC_RELATIONAL 2
 int  qe_run_queries_lanes(qe_ctx*, int workers, int executor, const char* text, char** out, size_t* outlen);
 /* A batch's shared sorts of whole base columns (no reference counterpart: the reference sorts a
  * base relation again for every join, src/join.c:122-142 + :5-94).  on = 1: from now on the first
@@ -160,6 +164,17 @@ int qe_filter_scan(qe_ctx*, qe_col col, char op, uint64_t v, qe_list* out);
 /* a2: exec_filter_rel_exists (src/filter.c:3-35): keep rowids r of `in` with col[r] op v, in
  * order (the count is the stray stdout line of src/filter.c:32; printing is the caller's). */
 int qe_filter_refine(qe_ctx*, qe_col col, char op, uint64_t v, qe_list* inout);
+/* keep positions i < n with colA[a[i]] == colB[b[i]] (a or b NULL: row i); compact the nl aligned
+ * uint32 lists in[0..nl) into outs[0..nl), order preserved; every list has n entries (so has a
+ * and b; nl >= 1).  No reference counterpart: the relational mode's selection inside a component
+ * (include/qe_plan.h select_eq).  One fused pass per launch loads the two rowid lists, gathers and
+ * compares the two values (the columns' u32 copies when both have one) and compacts two carried
+ * lists; further pairs of lists reuse the kept flags.  a and b may alias each other and lists of
+ * `in`; outs are new lists. */
+int qe_select_equal(qe_ctx*, qe_col colA, const qe_list* a, qe_col colB, const qe_list* b, int nl,
+                    const qe_list* const* in, qe_list* outs);
+/* elements per tile of qe_select_equal's compaction (its tests size their inputs around it) */
+uint32_t qe_select_equal_tile(void);
 /* a3/a4: allocate_relation / allocate_relation_mid_results (src/join.c:96-142):
  * (key = col[rowid], rowid) for rows == NULL (every row) or for each rowid of *rows in order. */
 int qe_gather_pairs(qe_ctx*, qe_col col, const qe_list* rows, qe_pairs* out);
@@ -295,6 +310,12 @@ int  qe_comm_stats(qe_comm*, uint64_t* exchanges, uint64_t* bytes_sent);
  * every rank).  Every rank passes the same text and relations; *out (rank 0) is the reference's
  * stdout; *refused = queries run the faithful way.  Returns 0, QE_EEXIT or an error. */
 int  qe_run_queries_dist(qe_ctx*, qe_comm*, const char* text, char** out, size_t* outlen, uint64_t* refused);
+/* Relational mode (include/qe_plan.h qe_plan_run_text_relational) on every rank of
+ * `comm` (NULL: one rank): *out (rank 0) holds one line per query with the textbook answer --
+ * oracle/truth.py's -- for every query shape, where qe_run_queries reproduces the reference's bytes.
+ * No fallback executor: QE_EINVAL / QE_ENOTSUP / QE_ETOOBIG end the batch with the output of the
+ * queries before.  qe_last_result_rows: the product of the component sizes, saturated. */
+int  qe_run_queries_relational(qe_ctx*, qe_comm*, const char* text, char** out, size_t* outlen);
 /* The in-process transport: nranks communicators over ctxs[0..nranks) (contexts of this process --
  * typically qe_workers of one ctx on ONE GPU, where RCCL refuses a second rank), each rank driven by
  * its own host thread.  Only the transport differs from qe_comm_init's: the counts all-to-all and the
@@ -310,6 +331,9 @@ int  qe_comm_init_local(qe_ctx* const* ctxs, int nranks, qe_comm** out);
  * sent to other ranks).  `queries` runs it with QE_LOCAL_RANKS=N. */
 int  qe_run_queries_local(qe_ctx*, int nranks, const char* text, char** out, size_t* outlen, uint64_t* refused,
                           uint64_t* bytes_sent);
+/* qe_run_queries_relational on nranks (1..16) in-process ranks, as qe_run_queries_local */
+int  qe_run_queries_relational_local(qe_ctx*, int nranks, const char* text, char** out, size_t* outlen,
+                                     uint64_t* bytes_sent);
 
 /* The ctx's HIP stream (hipStream_t), for callers that order their own work against it. */
 int qe_sync_stream_ptr(qe_ctx*, void** stream);

@@ -133,6 +133,14 @@ typedef struct qe_engine {
      * is still made on exactly one rank -- instead of exchanging the derived side and joining
      * bucket against bucket; the plan picks the cheaper by its cost model (QE_PLAN_BCAST). */
     int (*base_side_all)(void* u, uint32_t rel, uint32_t col, qe_h* keys, qe_h* rowids);
+    /* RELATIONAL MODE ONLY (the entry points below; the others never read it, so an engine built
+     * against the struct without it keeps working): keep the positions i with col_a[a[i]] ==
+     * col_b[b[i]] (columns of relations rel_a / rel_b; a and b rowid lists of one component, maybe
+     * the same list) and compact the n aligned uint32 lists (rowids or carried values) lists[0..n)
+     * into outs[0..n), order preserved.  Everything is borrowed; a and b are usually among `lists`.
+     * Rank-local: a component's lists are aligned per rank, so nothing is exchanged. */
+    int (*select_eq)(void* u, uint32_t rel_a, uint32_t col_a, qe_h a, uint32_t rel_b, uint32_t col_b, qe_h b, int n,
+                     const qe_h* lists, qe_h* outs);
 } qe_engine;
 
 /* Replay the reference's variant choice and list bookkeeping for every query of `text` on the
@@ -153,6 +161,22 @@ int qe_plan_run_text(const qe_engine* e, const char* text, char** out, size_t* o
  * planned when accepted, else (or on QE_ETOOBIG) through e->fallback; *refused = 1 then.  *rows
  * (nullable) as above.  (The concurrent batch runs its lanes' queries through this.) */
 int qe_plan_run_query(const qe_engine* e, void* query, void* out, uint64_t* rows, int* refused);
+
+/* Relational mode: every query's line is the textbook (SQL) answer -- what oracle/truth.py prints --
+ * whatever the reference prints for it.  Parsing is the shared one; neither
+ * qe_arrange_predicates nor the domain check runs, and there is no fallback.  Filters (column vs
+ * constant) run first wherever they are written and print no count line; column = column is a
+ * no-op (same binding and column), a filter (same binding), an equi-join (two components) or an
+ * in-component selection (e->select_eq, required); every binding of the query belongs to a
+ * component and a select prints sum(col over its component) x the sizes of the other components,
+ * mod 2^64, or NULL when the product of all sizes is 0.  *rows (nullable): that product, saturated.
+ * An error ends the batch with the output of the queries before it: QE_EINVAL (out-of-range
+ * relation / column / binding, no select), QE_ENOTSUP (column < or > column), QE_ETOOBIG (a join
+ * beyond the materialisation limit that no aggregate form covers).  The query_t of
+ * qe_plan_run_query_relational is a parsed one, arranged or not (the answer does not depend on the
+ * order of the predicates). */
+int qe_plan_run_text_relational(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows);
+int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uint64_t* rows);
 
 #ifdef __cplusplus
 }

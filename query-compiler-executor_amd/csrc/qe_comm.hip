@@ -884,6 +884,27 @@ int e_take(void* u, qe_h src, qe_h idx, qe_h* out) {
     });
 }
 
+// the relational mode's selection inside a component: one fused gather + compare + compaction of
+// every member list (qe_select_equal)
+int e_select_eq(void* u, uint32_t rel_a, uint32_t col_a, qe_h a, uint32_t rel_b, uint32_t col_b, qe_h b, int n,
+                const qe_h* lists, qe_h* outs) {
+    Eng* e = E(u);
+    return guard(e, [&] {
+        qe_ctx* c = e->c;
+        if (n < 1 || n > 64) throw Error(QE_EINVAL, "select_eq: 1..64 lists");
+        const qe_list la = as_list(A(a)), lb = as_list(A(b));
+        std::vector<qe_list> in(n), out(n);
+        std::vector<const qe_list*> inp(n);
+        for (int i = 0; i < n; i++) {
+            in[i] = as_list(A(lists[i]));
+            inp[i] = &in[i];
+        }
+        ck(qe_select_equal(c, column(c, rel_a, col_a), &la, column(c, rel_b, col_b), a == b ? &la : &lb, n, inp.data(),
+                           out.data()), c);
+        for (int i = 0; i < n; i++) outs[i] = H(new_arr(c, out[i].d, out[i].n, false));
+    });
+}
+
 int e_length(void* u, qe_h h, uint64_t* n) {
     (void)u;
     *n = A(h)->n;
@@ -1150,6 +1171,7 @@ qe_engine make_engine(Eng* e) {
         g.column = e_column;
         g.keys_of = e_keys_of;
     }
+    g.select_eq = e_select_eq;
     return g;
 }
 
@@ -1230,8 +1252,9 @@ int qe_comm_init_local(qe_ctx* const* ctxs, int nranks, qe_comm** out) {
     QE_API_END(c0)
 }
 
-int qe_run_queries_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen, uint64_t* refused,
-                         uint64_t* bytes_sent) {
+// qe_run_queries_local (relational = false) and qe_run_queries_relational_local over the same ranks
+static int run_local(qe_ctx* c, int nranks, bool relational, const char* text, char** out, size_t* outlen,
+                     uint64_t* refused, uint64_t* bytes_sent) {
     QE_API_BEGIN(c)
     *out = nullptr;
     *outlen = 0;
@@ -1253,8 +1276,14 @@ int qe_run_queries_local(qe_ctx* c, int nranks, const char* text, char** out, si
     for (int r = 0; r < nranks; r++)
         th.emplace_back([&, r] {
             qe_bind_thread(w[r]);
-            rcs[r] = qe_run_queries_dist(w[r], m[r], text, &outs[r], &lens[r], &ref[r]);
-            if (rcs[r] != 0 && rcs[r] != QE_EEXIT) m[r]->local->fail();   // never leave a peer waiting
+            rcs[r] = relational ? qe_run_queries_relational(w[r], m[r], text, &outs[r], &lens[r])
+                                : qe_run_queries_dist(w[r], m[r], text, &outs[r], &lens[r], &ref[r]);
+            // never leave a peer waiting -- but the codes that end a relational batch are every rank's
+            // (decided on the text alone, or all-reduced by the plan): a rank that leaves with one must
+            // not break the group while a peer is still inside the previous query's last collective
+            // (an engine call that fails on one rank alone has told the group already: peer_failed)
+            const bool agreed = relational && (rcs[r] == QE_EINVAL || rcs[r] == QE_ENOTSUP || rcs[r] == QE_ETOOBIG);
+            if (rcs[r] != 0 && rcs[r] != QE_EEXIT && !agreed) m[r]->local->fail();
         });
     for (auto& t : th) t.join();
     uint64_t sent = 0;
@@ -1281,6 +1310,16 @@ int qe_run_queries_local(qe_ctx* c, int nranks, const char* text, char** out, si
     *outlen = lens[0];
     return rc;
     QE_API_END(c)
+}
+
+int qe_run_queries_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen, uint64_t* refused,
+                         uint64_t* bytes_sent) {
+    return run_local(c, nranks, false, text, out, outlen, refused, bytes_sent);
+}
+
+int qe_run_queries_relational_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen,
+                                    uint64_t* bytes_sent) {
+    return run_local(c, nranks, true, text, out, outlen, nullptr, bytes_sent);
 }
 
 void qe_comm_fini(qe_comm* m) {
@@ -1390,6 +1429,26 @@ int qe_run_queries_dist(qe_ctx* c, qe_comm* m, const char* text, char** out, siz
     uint64_t rows = c->last_result_rows, nref = 0;
     int rc = qe_plan_run_text(&g, text, out, outlen, &rows, &nref);
     if (refused) *refused = nref;
+    c->last_result_rows = rows;
+    return rc;
+}
+
+int qe_run_queries_relational(qe_ctx* c, qe_comm* m, const char* text, char** out, size_t* outlen) {
+    if (!c) return QE_EINVAL;
+    Eng e{c, m, m ? m->nranks : 1, m ? m->rank : 0, 0};
+    qe_engine g = make_engine(&e);
+    uint64_t rows = c->last_result_rows;
+    const int rc = qe_plan_run_text_relational(&g, text, out, outlen, &rows);
+    if (rc != 0 && qe_plan_why()[0]) c->err = qe_plan_why();   // (a query refused before it ran)
+    c->last_result_rows = rows;
+    return rc;
+}
+
+int qe_plan_exec_query_relational(qe_ctx* c, query_t* q, FILE* out) {
+    Eng e{c, nullptr, 1, 0, 0};
+    qe_engine g = make_engine(&e);
+    uint64_t rows = c->last_result_rows;
+    const int rc = qe_plan_run_query_relational(&g, q, out, &rows);
     c->last_result_rows = rows;
     return rc;
 }

@@ -186,6 +186,91 @@ struct PrefixMaxHitOp {         // unsorted merge: index i where key[i] equals t
     }
 };
 
+// four consecutive list entries from element `base` (a multiple of 4; lists are dalloc blocks, so the
+// 16-byte load is aligned), zero past n
+__device__ __forceinline__ void load4_u32(const uint32_t* p, uint64_t base, uint64_t n, uint32_t* r) {
+    if (base + 3 < n) {
+        const uint4 x = *reinterpret_cast<const uint4*>(p + base);
+        r[0] = x.x; r[1] = x.y; r[2] = x.z; r[3] = x.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = base + k < n ? p[base + k] : 0u;
+    }
+}
+
+// The relational mode's selection inside a component (no reference counterpart): position i is kept
+// when colA[a[i]] == colB[b[i]], and the two carried lists in0 / in1 -- aligned with a and b, often a
+// and b themselves -- are compacted.  Each list is loaded once, coalesced (a list that is also a
+// carried one is not read twice); the two values are gathered as full 64-bit words, or from the
+// columns' u32 copies when BOTH columns have one (all their values below 2^32: the comparison of the
+// low words is then the comparison).  A rowid past its column never matches (no read past the
+// column).  keep (nullable): the kept flags of positions base..base+3 as one byte per thread step,
+// for the launches that carry a wider component's further lists (KeepCarryOp) without gathering again.
+struct SelectEqualOp {
+    static constexpr int VEC = 4;
+    const uint64_t *ca, *cb;
+    const uint32_t *ca32, *cb32;   // both set, or both null
+    uint64_t na, nb;               // the columns' rows
+    const uint32_t *a, *b;         // nullable: row i
+    const uint32_t *in0, *in1;     // in1 null when the launch carries one list
+    uint8_t* keep;
+    __device__ __forceinline__ void load(uint64_t base, uint64_t n, bool* f, uint32_t* v0, uint32_t* v1) const {
+        uint32_t ra[4], rb[4];
+        if (a) load4_u32(a, base, n, ra);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) ra[k] = (uint32_t)(base + k);
+        }
+        if (b == a) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) rb[k] = ra[k];
+        } else if (b) load4_u32(b, base, n, rb);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) rb[k] = (uint32_t)(base + k);
+        }
+        if (in0 == a && a) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) v0[k] = ra[k];
+        } else if (in0 == b && b) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) v0[k] = rb[k];
+        } else load4_u32(in0, base, n, v0);
+        if (in1) {
+            if (in1 == a && a) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) v1[k] = ra[k];
+            } else if (in1 == b && b) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) v1[k] = rb[k];
+            } else load4_u32(in1, base, n, v1);
+        }
+        uint32_t bits = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool ok = base + k < n && ra[k] < na && rb[k] < nb;
+            bool eq = false;
+            if (ok) eq = ca32 ? ca32[ra[k]] == cb32[rb[k]] : ca[ra[k]] == cb[rb[k]];
+            f[k] = eq;
+            bits |= (uint32_t)eq << k;
+        }
+        if (keep && base < n) keep[base >> 2] = (uint8_t)bits;
+    }
+};
+
+struct KeepCarryOp {            // two more lists of the component, by SelectEqualOp's kept flags
+    static constexpr int VEC = 4;
+    const uint8_t* keep;
+    const uint32_t *in0, *in1;  // in1 null when the launch carries one list
+    __device__ __forceinline__ void load(uint64_t base, uint64_t n, bool* f, uint32_t* v0, uint32_t* v1) const {
+        const uint32_t bits = base < n ? keep[base >> 2] : 0u;
+        load4_u32(in0, base, n, v0);
+        if (in1) load4_u32(in1, base, n, v1);
+#pragma unroll
+        for (int k = 0; k < 4; k++) f[k] = (bits >> k) & 1u;
+    }
+};
+
 // ---- the kernel -------------------------------------------------------------------------------
 #ifdef QE_DIAG_STAMPS
 __device__ uint64_t g_cp_stamps[STAMP_TILES * STAMP_SLOTS];
@@ -763,4 +848,92 @@ uint64_t compact_prefix_max_hits(qe_ctx* c, const uint64_t* key, const uint64_t*
     return run_compact<4, 1>(c, "seq_merge", 16.0 * n, PrefixMaxHitOp{key, pmax, limit}, n, out, nullptr);
 }
 
+// ---- select_equal (relational mode) --------------------------------------------------------------
+// A launch carries two lists: the shared pipeline stages NOUT x TILE survivors in LDS and keeps
+// f / v0 / v1 / rank for ITEMS x VEC elements per thread in registers.  SE_ITEMS = 4: a tile of
+// 8192 positions, 64 KiB of LDS for two lists (two workgroups per CU), half the refine's registers
+// for the second gather's addresses.  Algorithmic bytes: each distinct list read once (4 B), two
+// gathered values (8 B each, 4 B from the u32 copies), the flags byte per 4 positions when a wider
+// component needs it, 4 B per list per survivor (added by run_compact).
+#ifndef QE_SE_ITEMS
+#define QE_SE_ITEMS 4
+#endif
+constexpr int SE_ITEMS = QE_SE_ITEMS;
+constexpr uint32_t SE_TILE = CB * SE_ITEMS * SelectEqualOp::VEC;
+
+// outs[0..nl): dalloc blocks of n entries; returns the survivors' count
+static uint64_t select_equal(qe_ctx* c, qe_col colA, const uint32_t* a, qe_col colB, const uint32_t* b, uint64_t n,
+                             int nl, const uint32_t* const* in, uint32_t* const* outs) {
+    if (n == 0) return 0;
+    const uint32_t* a32 = narrow_of(c, colA.d, colA.n);
+    const uint32_t* b32 = narrow_of(c, colB.d, colB.n);
+    if (!a32 || !b32) a32 = b32 = nullptr;   // a value of 2^32 or more somewhere: full words
+    uint8_t* keep = nl > 2 ? dalloc_t<uint8_t>(c, (n + 3) / 4) : nullptr;
+    uint64_t m = 0;
+    try {
+        int lists = 1 + (b != a) + (in[0] != a && in[0] != b) + (nl > 1 && in[1] != a && in[1] != b);
+        if (!a) lists--;
+        if (!b && a) lists--;
+        const double bytes = (4.0 * lists + (a32 ? 8.0 : 16.0) + (keep ? 0.25 : 0.0)) * (double)n;
+        const SelectEqualOp op{colA.d, colB.d, a32, b32, colA.n, colB.n, a, b, in[0], nl > 1 ? in[1] : nullptr, keep};
+        if (nl > 1) m = run_compact<SE_ITEMS, 2>(c, "select_equal", bytes, op, n, outs[0], outs[1]);
+        else m = run_compact<SE_ITEMS, 1>(c, "select_equal", bytes, op, n, outs[0], nullptr);
+        for (int k = 2; k < nl; k += 2) {   // the further lists, two per launch, by the kept flags
+            const bool two = k + 1 < nl;
+            const KeepCarryOp kc{keep, in[k], two ? in[k + 1] : nullptr};
+            const double kb = (0.25 + (two ? 8.0 : 4.0)) * (double)n;
+            const uint64_t mk = two ? run_compact<SE_ITEMS, 2>(c, "select_equal", kb, kc, n, outs[k], outs[k + 1])
+                                    : run_compact<SE_ITEMS, 1>(c, "select_equal", kb, kc, n, outs[k], nullptr);
+            if (mk != m) throw Error(QE_EINVAL, "select_equal: carried lists disagree on the survivors");
+        }
+    } catch (...) {
+        if (keep) dfree(c, keep);
+        throw;
+    }
+    if (keep) dfree(c, keep);
+    return m;
+}
+
 }  // namespace qe
+
+using namespace qe;
+
+extern "C" {
+
+uint32_t qe_select_equal_tile(void) { return SE_TILE; }
+
+int qe_select_equal(qe_ctx* c, qe_col colA, const qe_list* a, qe_col colB, const qe_list* b, int nl,
+                    const qe_list* const* in, qe_list* outs) {
+    QE_API_BEGIN(c)
+    if (nl < 1 || nl > 64 || !in || !in[0] || !outs || !colA.d || !colB.d) throw Error(QE_EINVAL, "select_equal: bad arguments");
+    const uint64_t n = in[0]->n;
+    for (int k = 0; k < nl; k++)
+        if (!in[k] || in[k]->n != n || (n && !in[k]->d)) throw Error(QE_EINVAL, "select_equal: lists of different lengths");
+    if ((a && a->n != n) || (b && b->n != n)) throw Error(QE_EINVAL, "select_equal: lists of different lengths");
+    if ((!a && n > colA.n) || (!b && n > colB.n)) throw Error(QE_EINVAL, "select_equal: more positions than rows");
+    if (n >> 32) throw Error(QE_EINVAL, "select_equal: input too large");
+    const uint32_t* ind[64];
+    uint32_t* outd[64];
+    int made = 0;
+    try {
+        for (; made < nl; made++) {
+            outd[made] = dalloc_t<uint32_t>(c, std::max<uint64_t>(n, 1));
+            ind[made] = in[made]->d;
+        }
+        const uint64_t m = select_equal(c, colA, a ? a->d : nullptr, colB, b ? b->d : nullptr, n, nl, ind, outd);
+        for (int k = 0; k < nl; k++) {
+            const uint32_t flags = in[k]->flags & QE_LIST_DISTINCT;   // (read before outs[k] is written: it may be in[k])
+            outs[k].d = outd[k];
+            outs[k].n = m;
+            outs[k].cap = n;
+            outs[k].flags = flags;
+        }
+    } catch (...) {
+        for (int k = 0; k < made; k++) dfree(c, outd[k]);
+        throw;
+    }
+    return 0;
+    QE_API_END(c)
+}
+
+}  // extern "C"

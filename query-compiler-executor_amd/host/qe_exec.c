@@ -727,6 +727,7 @@ typedef struct {
     int* rcs;
     atomic_int* stop;          /* the first query index known to end the batch (+1), 0 none */
     int plan;                  /* QE_EXEC_PLAN: the partitioned plan, faithful fallback */
+    int relational;            /* QE_EXEC_RELATIONAL: the plan's relational mode, no fallback */
 } lane_t;
 
 static void* lane_main(void* arg) {
@@ -744,8 +745,10 @@ static void* lane_main(void* arg) {
         if (!f) {
             L->rcs[i] = QE_ENOMEM;
         } else {
-            qe_arrange_predicates(&L->qs[i]);
-            L->rcs[i] = L->plan ? qe_plan_exec_query(L->ctx, &L->qs[i], f) : qe_exec_query(L->ctx, &L->qs[i], f);
+            if (!L->relational) qe_arrange_predicates(&L->qs[i]);
+            L->rcs[i] = L->relational ? qe_plan_exec_query_relational(L->ctx, &L->qs[i], f)
+                        : L->plan     ? qe_plan_exec_query(L->ctx, &L->qs[i], f)
+                                      : qe_exec_query(L->ctx, &L->qs[i], f);
             fclose(f);
         }
         if (L->rcs[i] != 0) {                   /* remember the earliest failing query */
@@ -764,13 +767,16 @@ int qe_run_queries_parallel(qe_ctx* ctx, int workers, const char* text, char** o
 int qe_run_queries_lanes(qe_ctx* ctx, int workers, int executor, const char* text, char** out, size_t* outlen) {
     *out = NULL;
     *outlen = 0;
-    if (executor != QE_EXEC_FAITHFUL && executor != QE_EXEC_PLAN) return QE_EINVAL;
-    const int plan = executor == QE_EXEC_PLAN;
+    if (executor != QE_EXEC_FAITHFUL && executor != QE_EXEC_PLAN && executor != QE_EXEC_RELATIONAL) return QE_EINVAL;
+    const int relational = executor == QE_EXEC_RELATIONAL;
+    const int plan = executor == QE_EXEC_PLAN || relational;   /* (the plan's engine, its shared sorts) */
     if (workers <= 1) {
         if (!plan) return qe_run_queries(ctx, text, out, outlen);
         uint64_t refused = 0;
         int rc = qe_sort_cache(ctx, 1);          /* the batch's base-column sorts, shared */
-        if (rc == 0) rc = qe_run_queries_dist(ctx, NULL, text, out, outlen, &refused);
+        if (rc == 0)
+            rc = relational ? qe_run_queries_relational(ctx, NULL, text, out, outlen)
+                            : qe_run_queries_dist(ctx, NULL, text, out, outlen, &refused);
         const int rc2 = qe_sort_cache(ctx, 0);
         return rc != 0 ? rc : rc2;
     }
@@ -789,7 +795,7 @@ int qe_run_queries_lanes(qe_ctx* ctx, int workers, int executor, const char* tex
     pthread_t th[16];
     int started = 0;
     for (int k = 0; k < workers; k++) {
-        lane_t l = {w[k], qs, nq, &next, outs, lens, rcs, &stop, plan};
+        lane_t l = {w[k], qs, nq, &next, outs, lens, rcs, &stop, plan, relational};
         lanes[k] = l;
         if (pthread_create(&th[k], NULL, lane_main, &lanes[k]) == 0) started++;
         else break;

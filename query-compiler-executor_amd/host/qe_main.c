@@ -19,6 +19,11 @@
  *                 qe_run_queries_lanes)
  *   QE_LOCAL_RANKS=N  (one GPU, N >= 2) the partitioned executor on N in-process ranks of this GPU
  *                 (qe_run_queries_local: the multi-GPU data path with its exchanges, rehearsed)
+ *   QE_RELATIONAL=1  relational mode: one line per query with the textbook (SQL) answer, for every
+ *                 query shape -- also where the reference prints something else or exits -- and no
+ *                 filter count lines (include/qe_plan.h); with QE_WORKERS,
+ *                 QE_LOCAL_RANKS and QE_GPUS as above (QE_PLAN is not read).  A query it cannot
+ *                 answer ends the batch: the lines of the queries before it, then EXIT_LIBQE.
  *
  * Exit status: 0; 1 where the reference calls exit(EXIT_FAILURE); EXIT_LIBQE (70, sysexits'
  * EX_SOFTWARE) when libqe reports an error (a message on stderr); a rank of QE_GPUS=N killed by
@@ -165,7 +170,8 @@ static int run_rank(const input_t* in, int rank, int world, int* to_peers, int f
     char* out = NULL;
     size_t outlen = 0;
     uint64_t refused = 0;
-    int rc = qe_run_queries_dist(c, m, in->text, &out, &outlen, &refused);
+    int rc = env_int("QE_RELATIONAL", 0, 0, 1) ? qe_run_queries_relational(c, m, in->text, &out, &outlen)
+                                               : qe_run_queries_dist(c, m, in->text, &out, &outlen, &refused);
     int status = finish(rc, out, outlen, rank == 0);
     qe_comm_fini(m);
     qe_fini(c);
@@ -270,13 +276,15 @@ int main(void) {
     size_t outlen = 0;
     const int plan = env_int("QE_PLAN", 1, 0, 1);
     const int lranks = env_int("QE_LOCAL_RANKS", 0, 0, 16);
+    const int relational = env_int("QE_RELATIONAL", 0, 0, 1);
     int rc;
     if (lranks >= 2) {
         uint64_t refused = 0, sent = 0;
-        rc = qe_run_queries_local(c, lranks, in.text, &out, &outlen, &refused, &sent);
+        rc = relational ? qe_run_queries_relational_local(c, lranks, in.text, &out, &outlen, &sent)
+                        : qe_run_queries_local(c, lranks, in.text, &out, &outlen, &refused, &sent);
     } else {
-        rc = qe_run_queries_lanes(c, env_int("QE_WORKERS", 8, 1, 16), plan ? QE_EXEC_PLAN : QE_EXEC_FAITHFUL, in.text,
-                                  &out, &outlen);
+        const int executor = relational ? QE_EXEC_RELATIONAL : plan ? QE_EXEC_PLAN : QE_EXEC_FAITHFUL;
+        rc = qe_run_queries_lanes(c, env_int("QE_WORKERS", 8, 1, 16), executor, in.text, &out, &outlen);
     }
     int status = finish(rc, out, outlen, 1);
     qe_fini(c);

@@ -2,7 +2,9 @@
  * qe_plan.c -- the key-partitioned plan of include/qe_plan.h: (1) the domain check, a replay of
  * the reference's mid_result state machine on bindings alone, and (2) the relational plan itself
  * over an engine (filters on rank slices, hash exchange of derived join sides, local sort-merge
- * joins, all-reduced checksums).  Host C; the engine does every row-sized step.
+ * joins, all-reduced checksums), and (3) the relational mode: the same plan with its own predicate
+ * ordering, selections inside a component and cross-product arithmetic, for every query shape and
+ * without the domain check or a fallback.  Host C; the engine does every row-sized step.
  *
  * Reference anchors: execute_query src/utilities.c:258-287, execute_filter src/filter.c:66-100,
  * build_relations src/join.c:152-292, update_mid_results src/join.c:507-628, fix_all_mid_results
@@ -913,6 +915,90 @@ static int join_key_hint(const query_t* q, int b) {
     return kc < 256 ? kc : 0;
 }
 
+/* The hints do_join / side_start take for join jp, which has just left the pending list: what
+ * reads each binding afterwards -- the joins still pending (pending[0..np)), the predicates after
+ * this run of joins (preds[end..)) and the selects. */
+static void join_hints(const plan_t* P, const pred_t* jp, const int* pending, size_t np, size_t end, uint8_t* need,
+                       int* sel1, int* kcol1, int* vok) {
+    const query_t* q = P->q;
+    const size_t nb = q->nrels + 1;
+    /* bindings read later: the remaining joins, later predicates, the selects */
+    memset(need, 0, nb);
+    for (size_t s = 0; s < q->nsel; s++) need[q->sel[2 * s]] = 1;
+    for (size_t i = 0; i < np; i++) {
+        need[q->preds[pending[i]].frel] = 1;
+        need[q->preds[pending[i]].srel] = 1;
+    }
+    for (size_t i = end; i < q->npreds; i++) {
+        need[q->preds[i].frel] = 1;
+        if (q->preds[i].type == 0) need[q->preds[i].srel] = 1;
+    }
+    /* sel1[b] = c + 1: after this join, binding b is read only by selects, all of column c */
+    for (size_t x = 0; x < nb; x++) sel1[x] = 0;
+    for (size_t s = 0; s < q->nsel; s++) {
+        const size_t x = q->sel[2 * s];
+        const int cv = (int)q->sel[2 * s + 1] + 1;
+        sel1[x] = sel1[x] == 0 ? cv : sel1[x] == cv ? cv : -1;
+    }
+    for (size_t i = 0; i < np; i++) {
+        sel1[q->preds[pending[i]].frel] = -1;
+        sel1[q->preds[pending[i]].srel] = -1;
+    }
+    for (size_t i = end; i < q->npreds; i++) {
+        sel1[q->preds[i].frel] = -1;
+        if (q->preds[i].type == 0) sel1[q->preds[i].srel] = -1;
+    }
+    for (size_t x = 0; x < nb; x++)
+        if (sel1[x] < 0) sel1[x] = 0;
+    /* kcol1[b] = c + 1: binding b joins again after this join, always on its column c */
+    for (size_t x = 0; x < nb; x++) kcol1[x] = 0;
+    for (size_t i = 0; i < np + (q->npreds - end); i++) {
+        const pred_t* r = i < np ? &q->preds[pending[i]] : &q->preds[end + (i - np)];
+        if (r->type != 0) continue;
+        const size_t xs[2] = {r->frel, r->srel};
+        const int cs2[2] = {(int)r->fcol + 1, (int)r->scol + 1};
+        for (int t = 0; t < 2; t++)
+            kcol1[xs[t]] = kcol1[xs[t]] == 0 ? cs2[t] : kcol1[xs[t]] == cs2[t] ? cs2[t] : -1;
+    }
+    for (size_t x = 0; x < nb; x++)
+        if (kcol1[x] < 0) kcol1[x] = 0;
+    /* vok[b] = c + 1 (b one of this join's bindings): every select of b reads column c, no
+     * later filter reads b, and the one remaining join touching the merged component is
+     * b's, on kcol1[b] -- so b's next join takes its key from the payload and nothing
+     * after it needs b's rowids: b may ride as column c's values */
+    for (size_t x = 0; x < nb; x++) vok[x] = 0;
+    {
+        const int ca = P->comp_of[jp->frel], cb2 = P->comp_of[jp->srel];
+        uint8_t* inm = (uint8_t*)calloc(nb, 1);
+        for (size_t x = 0; x < nb; x++)
+            inm[x] = x == jp->frel || x == jp->srel || (P->comp_of[x] >= 0 && (P->comp_of[x] == ca || P->comp_of[x] == cb2));
+        int touching = 0;
+        const pred_t* only = NULL;
+        for (size_t i = 0; i < np + (q->npreds - end); i++) {
+            const pred_t* r = i < np ? &q->preds[pending[i]] : &q->preds[end + (i - np)];
+            if (r->type != 0) continue;
+            if (inm[r->frel] || inm[r->srel]) {
+                touching++;
+                only = r;
+            }
+        }
+        const size_t ends[2] = {jp->frel, jp->srel};
+        for (int t = 0; t < 2 && touching == 1; t++) {
+            const size_t x = ends[t];
+            const int on_x = (only->frel == x && (int)only->fcol + 1 == kcol1[x] && !inm[only->srel]) ||
+                             (only->srel == x && (int)only->scol + 1 == kcol1[x] && !inm[only->frel]);
+            if (!on_x || !kcol1[x]) continue;
+            int c1 = 0;
+            for (size_t s = 0; s < q->nsel; s++)
+                if (q->sel[2 * s] == x) c1 = c1 == 0 || c1 == (int)q->sel[2 * s + 1] + 1 ? (int)q->sel[2 * s + 1] + 1 : -1;
+            for (size_t i = end; i < q->npreds; i++)
+                if (q->preds[i].type == 1 && q->preds[i].frel == x) c1 = -1;
+            vok[x] = c1 > 0 ? c1 : 0;
+        }
+        free(inm);
+    }
+}
+
 static int plan_query(const qe_engine* e, const query_t* q, FILE* out, uint64_t* rows_out) {
     plan_t PP;
     plan_t* P = &PP;
@@ -992,81 +1078,7 @@ static int plan_query(const qe_engine* e, const query_t* q, FILE* out, uint64_t*
             const pred_t* jp = &q->preds[pending[jbest]];
             for (size_t i = jbest; i + 1 < np; i++) pending[i] = pending[i + 1];
             np--;
-            /* bindings read later: the remaining joins, later predicates, the selects */
-            memset(need, 0, nb);
-            for (size_t s = 0; s < q->nsel; s++) need[q->sel[2 * s]] = 1;
-            for (size_t i = 0; i < np; i++) {
-                need[q->preds[pending[i]].frel] = 1;
-                need[q->preds[pending[i]].srel] = 1;
-            }
-            for (size_t i = end; i < q->npreds; i++) {
-                need[q->preds[i].frel] = 1;
-                if (q->preds[i].type == 0) need[q->preds[i].srel] = 1;
-            }
-            /* sel1[b] = c + 1: after this join, binding b is read only by selects, all of column c */
-            for (size_t x = 0; x < nb; x++) sel1[x] = 0;
-            for (size_t s = 0; s < q->nsel; s++) {
-                const size_t x = q->sel[2 * s];
-                const int cv = (int)q->sel[2 * s + 1] + 1;
-                sel1[x] = sel1[x] == 0 ? cv : sel1[x] == cv ? cv : -1;
-            }
-            for (size_t i = 0; i < np; i++) {
-                sel1[q->preds[pending[i]].frel] = -1;
-                sel1[q->preds[pending[i]].srel] = -1;
-            }
-            for (size_t i = end; i < q->npreds; i++) {
-                sel1[q->preds[i].frel] = -1;
-                if (q->preds[i].type == 0) sel1[q->preds[i].srel] = -1;
-            }
-            for (size_t x = 0; x < nb; x++)
-                if (sel1[x] < 0) sel1[x] = 0;
-            /* kcol1[b] = c + 1: binding b joins again after this join, always on its column c */
-            for (size_t x = 0; x < nb; x++) kcol1[x] = 0;
-            for (size_t i = 0; i < np + (q->npreds - end); i++) {
-                const pred_t* r = i < np ? &q->preds[pending[i]] : &q->preds[end + (i - np)];
-                if (r->type != 0) continue;
-                const size_t xs[2] = {r->frel, r->srel};
-                const int cs2[2] = {(int)r->fcol + 1, (int)r->scol + 1};
-                for (int t = 0; t < 2; t++)
-                    kcol1[xs[t]] = kcol1[xs[t]] == 0 ? cs2[t] : kcol1[xs[t]] == cs2[t] ? cs2[t] : -1;
-            }
-            for (size_t x = 0; x < nb; x++)
-                if (kcol1[x] < 0) kcol1[x] = 0;
-            /* vok[b] = c + 1 (b one of this join's bindings): every select of b reads column c, no
-             * later filter reads b, and the one remaining join touching the merged component is
-             * b's, on kcol1[b] -- so b's next join takes its key from the payload and nothing
-             * after it needs b's rowids: b may ride as column c's values */
-            for (size_t x = 0; x < nb; x++) vok[x] = 0;
-            {
-                const int ca = P->comp_of[jp->frel], cb2 = P->comp_of[jp->srel];
-                uint8_t* inm = (uint8_t*)calloc(nb, 1);
-                for (size_t x = 0; x < nb; x++)
-                    inm[x] = x == jp->frel || x == jp->srel || (P->comp_of[x] >= 0 && (P->comp_of[x] == ca || P->comp_of[x] == cb2));
-                int touching = 0;
-                const pred_t* only = NULL;
-                for (size_t i = 0; i < np + (q->npreds - end); i++) {
-                    const pred_t* r = i < np ? &q->preds[pending[i]] : &q->preds[end + (i - np)];
-                    if (r->type != 0) continue;
-                    if (inm[r->frel] || inm[r->srel]) {
-                        touching++;
-                        only = r;
-                    }
-                }
-                const size_t ends[2] = {jp->frel, jp->srel};
-                for (int t = 0; t < 2 && touching == 1; t++) {
-                    const size_t x = ends[t];
-                    const int on_x = (only->frel == x && (int)only->fcol + 1 == kcol1[x] && !inm[only->srel]) ||
-                                     (only->srel == x && (int)only->scol + 1 == kcol1[x] && !inm[only->frel]);
-                    if (!on_x || !kcol1[x]) continue;
-                    int c1 = 0;
-                    for (size_t s = 0; s < q->nsel; s++)
-                        if (q->sel[2 * s] == x) c1 = c1 == 0 || c1 == (int)q->sel[2 * s + 1] + 1 ? (int)q->sel[2 * s + 1] + 1 : -1;
-                    for (size_t i = end; i < q->npreds; i++)
-                        if (q->preds[i].type == 1 && q->preds[i].frel == x) c1 = -1;
-                    vok[x] = c1 > 0 ? c1 : 0;
-                }
-                free(inm);
-            }
+            join_hints(P, jp, pending, np, end, need, sel1, kcol1, vok);
             rc = do_join(P, jp, need, sel1, kcol1, vok, np == 0 && end == q->npreds);
         }
         k = end;
@@ -1120,6 +1132,293 @@ static int plan_query(const qe_engine* e, const query_t* q, FILE* out, uint64_t*
     free(scol);
     free(srows);
     free(ssize);
+    for (int i = 0; i < P->nc; i++)
+        if (P->C[i].alive) free_comp(P, i);
+    for (size_t b = 0; b < nb; b++) rel(P, P->list[b]);
+    free(P->C);
+    free(P->comp_of);
+    free(P->list);
+    free(P->list_size);
+    free(need);
+    free(sel1);
+    free(kcol1);
+    free(vok);
+    free(pending);
+    return rc ? rc : P->rc;
+}
+
+/* ============================================================================================ */
+/* (3) relational mode: the textbook answer for every query shape (qe_plan.h)       */
+/* ============================================================================================ */
+
+/* QE_EINVAL / QE_ENOTSUP with the reason, or 0: every rank decides on the text and the relations'
+ * shapes alone, so all of them leave a bad query together before any collective */
+static int rel_validate(const qe_engine* e, const query_t* q) {
+    g_why[0] = 0;
+    if (!e->select_eq) return refuse("the engine has no select_eq"), QE_EINVAL;
+    if (!s_query_valid(e, q)) return refuse("out-of-range relation / column / binding"), QE_EINVAL;
+    if (q->nsel == 0) return refuse("no select"), QE_EINVAL;
+    if (q->nrels > 60) return refuse("more than 60 bindings"), QE_EINVAL;   /* (side_t's carried bindings) */
+    for (size_t i = 0; i < q->npreds; i++) {
+        const pred_t* p = &q->preds[i];
+        if (!op_valid(p->op)) return refuse("operator '%c'", p->op), QE_EINVAL;
+        if (p->type == 0 && p->op != '=')   /* (the reference joins on equality whatever is written) */
+            return refuse("column %c column is not an equi-join", p->op);
+    }
+    return 0;
+}
+
+/* does some column = column predicate of q run inside a component, whatever the join order?  A
+ * predicate on one binding does, and so does one of every cycle of the join graph (and of every pair
+ * of predicates between the same two bindings) */
+static int rel_has_selection(const query_t* q) {
+    int* parent = (int*)malloc((q->nrels + 1) * sizeof(int));
+    for (size_t i = 0; i <= q->nrels; i++) parent[i] = (int)i;
+    int found = 0;
+    for (size_t i = 0; !found && i < q->npreds; i++) {
+        const pred_t* p = &q->preds[i];
+        if (p->type != 0) continue;
+        const int a = uf_find(parent, (int)p->frel), b = uf_find(parent, (int)p->srel);
+        if (a == b) found = 1;
+        else parent[a] = b;
+    }
+    free(parent);
+    return found;
+}
+
+/* this rank's rowid list of binding b, its whole slice when nothing filtered it yet */
+static int rel_list_of(plan_t* P, int b) {
+    if (P->list[b] != NONE) return 0;
+    uint64_t s, t;
+    owned_range(P, rel_rows(P, P->q->rels[b]), &s, &t);
+    ECHK(P->e->iota(P->e->u, s, t - s, &P->list[b]));
+    return 0;
+}
+
+/* every filter of binding b (column vs constant, wherever it is written; they AND), then its
+ * column = column predicates on itself -- before b takes part in any join; no count line printed
+ * (src/filter.c:32 is the reference's stray output, not the answer) */
+static int rel_filter_binding(plan_t* P, int b, int hints) {
+    const qe_engine* e = P->e;
+    const query_t* q = P->q;
+    const uint32_t relid = q->rels[b];
+    int touched = 0;
+    size_t nf = 0;
+    const pred_t** f = (const pred_t**)malloc((q->npreds + 1) * sizeof(*f));
+    for (size_t i = 0; i < q->npreds; i++)
+        if (q->preds[i].type == 1 && (int)q->preds[i].frel == b) f[nf++] = &q->preds[i];
+    int frc = 0;
+    size_t k = 0;
+    if (nf) {                                                /* the first two in one fused scan, the rest refine it */
+        uint64_t s, t;
+        owned_range(P, rel_rows(P, relid), &s, &t);
+        touched = 1;
+        if (nf >= 2 && e->scan2) {
+            const int vh = hints && values_hint(q, b, f[0]->fcol) && e->values != NULL;
+            frc = e->scan2(e->u, relid, (uint32_t)f[0]->fcol, f[0]->op, f[0]->cval, (uint32_t)f[1]->fcol, f[1]->op,
+                           f[1]->cval, s, t, vh | (hints ? join_key_hint(q, b) << 8 : 0), &P->list[b]);
+            k = 2;
+        } else {
+            frc = e->scan(e->u, relid, (uint32_t)f[0]->fcol, s, t, f[0]->op, f[0]->cval, &P->list[b]);
+            k = 1;
+        }
+    }
+    for (; frc == 0 && k < nf; k++) {
+        qe_h nl = NONE;
+        frc = e->refine(e->u, relid, (uint32_t)f[k]->fcol, P->list[b], f[k]->op, f[k]->cval, &nl);
+        P->list[b] = nl;
+    }
+    free(f);
+    ECHK(frc);
+    for (size_t i = 0; i < q->npreds; i++) {                 /* b.x = b.y: a filter on b's rows */
+        const pred_t* p = &q->preds[i];
+        if (p->type != 0 || (int)p->frel != b || (int)p->srel != b || p->fcol == p->scol) continue;
+        touched = 1;
+        ECHK(rel_list_of(P, b));
+        qe_h nl = NONE;
+        ECHK(e->select_eq(e->u, relid, (uint32_t)p->fcol, P->list[b], relid, (uint32_t)p->scol, P->list[b], 1,
+                          &P->list[b], &nl));
+        rel(P, P->list[b]);
+        P->list[b] = nl;
+    }
+    if (touched) {
+        uint64_t n = 0;
+        ECHK(e->length(e->u, P->list[b], &n));
+        ECHK(allreduce1(P, &n));
+        P->list_size[b] = n;
+    }
+    return 0;
+}
+
+/* a predicate between two bindings of one component: keep the component's rows where the two
+ * values are equal -- every member list compacted alike, on this rank alone (the lists are aligned
+ * per rank).  Key values delivered for a next join (kvals) are not carried: dropped. */
+static int rel_select_in_comp(plan_t* P, const pred_t* p) {
+    const qe_engine* e = P->e;
+    comp_t* c = &P->C[P->comp_of[p->frel]];
+    const int ia = member_idx(c, (int)p->frel), ib = member_idx(c, (int)p->srel);
+    if (ia < 0 || ib < 0 || c->m[ia].vcol || c->m[ib].vcol) {
+        P->rc = QE_EINVAL;                                   /* (a reader of rowids that the hints missed) */
+        return refuse("internal: binding of an in-component predicate was not carried as rowids"), QE_EINVAL;
+    }
+    qe_h in[64], outs[64];
+    for (int i = 0; i < c->n; i++) {
+        ECHK(rows_of(P, &c->m[i]));
+        rel(P, c->m[i].kvals);
+        c->m[i].kvals = NONE;
+        c->m[i].kcol = 0;
+        in[i] = c->m[i].rows;
+        outs[i] = NONE;
+    }
+    ECHK(e->select_eq(e->u, P->q->rels[p->frel], (uint32_t)p->fcol, c->m[ia].rows, P->q->rels[p->srel],
+                      (uint32_t)p->scol, c->m[ib].rows, c->n, in, outs));
+    for (int i = 0; i < c->n; i++) {
+        rel(P, c->m[i].rows);
+        c->m[i].rows = outs[i];
+    }
+    uint64_t n = 0;
+    ECHK(e->length(e->u, outs[0], &n));
+    ECHK(allreduce1(P, &n));
+    c->size = n;
+    return 0;
+}
+
+static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint64_t* rows_out) {
+    int rc = rel_validate(e, q);
+    if (rc) return rc;
+    plan_t PP;
+    plan_t* P = &PP;
+    memset(P, 0, sizeof *P);
+    P->e = e;
+    P->q = q;
+    const size_t nb = q->nrels + 1;
+    P->C = (comp_t*)calloc(2 * nb + q->npreds + 1, sizeof(comp_t));
+    P->comp_of = (int*)malloc(nb * sizeof(int));
+    P->list = (qe_h*)calloc(nb, sizeof(qe_h));
+    P->list_size = (uint64_t*)calloc(nb, sizeof(uint64_t));
+    for (size_t i = 0; i < nb; i++) P->comp_of[i] = -1;
+    const char* bm = getenv("QE_PLAN_BCAST");
+    P->bcast_mode = bm && (bm[0] == '0' || bm[0] == '2') ? bm[0] - '0' : 1;
+    P->reorder = !(getenv("QE_DIST_REORDER") && getenv("QE_DIST_REORDER")[0] == '0');
+    uint8_t* need = (uint8_t*)calloc(nb, 1);
+    int* sel1 = (int*)calloc(nb, sizeof(int));
+    int* kcol1 = (int*)calloc(nb, sizeof(int));
+    int* vok = (int*)calloc(nb, sizeof(int));
+    int* pending = (int*)malloc((q->npreds + 1) * sizeof(int));
+    /* a query with a selection inside a component: its bindings' rowids are read by a predicate
+     * that is no join, so no binding rides as its next join's key or as a column's values on the
+     * strength of "its only remaining predicate is a join" (kcol1 / vok / the scans' hints off) */
+    const int selection = rel_has_selection(q);
+    int zero = 0;                                            /* some component is empty: every select is NULL */
+    for (size_t b = 0; rc == 0 && b < q->nrels; b++) {
+        rc = rel_filter_binding(P, (int)b, !selection);
+        if (rc == 0 && (P->list[b] != NONE ? P->list_size[b] : rel_rows(P, q->rels[b])) == 0) zero = 1;
+    }
+    size_t np = 0;
+    for (size_t i = 0; i < q->npreds; i++)
+        if (q->preds[i].type == 0 && q->preds[i].frel != q->preds[i].srel) pending[np++] = (int)i;
+    while (rc == 0 && !zero && np) {
+        size_t jbest = np;
+        for (size_t i = 0; i < np; i++) {                    /* inside one component: it only shrinks it, at once */
+            const pred_t* r = &q->preds[pending[i]];
+            if (P->comp_of[r->frel] >= 0 && P->comp_of[r->frel] == P->comp_of[r->srel]) {
+                jbest = i;
+                break;
+            }
+        }
+        const int inside = jbest < np;
+        if (!inside) {
+            jbest = 0;
+            if (P->reorder) {                                /* greedy: the smallest |A| + |B| first */
+                uint64_t best = UINT64_MAX;
+                for (size_t i = 0; i < np; i++) {
+                    const uint64_t c = join_cost(P, &q->preds[pending[i]]);
+                    if (c < best) { best = c; jbest = i; }
+                }
+            }
+        }
+        const pred_t* jp = &q->preds[pending[jbest]];
+        for (size_t i = jbest; i + 1 < np; i++) pending[i] = pending[i + 1];
+        np--;
+        if (inside) {
+            rc = rel_select_in_comp(P, jp);
+            if (rc == 0 && P->C[P->comp_of[jp->frel]].size == 0) zero = 1;
+            continue;
+        }
+        join_hints(P, jp, pending, np, q->npreds, need, sel1, kcol1, vok);
+        if (selection) {
+            memset(kcol1, 0, nb * sizeof(int));
+            memset(vok, 0, nb * sizeof(int));
+        }
+        rc = do_join(P, jp, need, sel1, kcol1, vok, np == 0);
+        if (rc == 0 && (P->agg ? P->agg_size : P->C[P->comp_of[jp->frel]].size) == 0) zero = 1;
+    }
+    /* every binding belongs to a component: one no predicate joined is its list, or its whole relation */
+    for (size_t b = 0; rc == 0 && !zero && b < q->nrels; b++)
+        if (P->comp_of[b] < 0) (void)component(P, (int)b);
+    /* total = the product of the component sizes (the aggregate last join's pair count is one);
+     * a select prints its component's sum times the other components' sizes, mod 2^64 */
+    uint64_t* sums = (uint64_t*)calloc(q->nsel + 1, sizeof(uint64_t));
+    uint64_t* mult = (uint64_t*)calloc(q->nsel + 1, sizeof(uint64_t));
+    uint32_t* srel = (uint32_t*)calloc(q->nsel + 1, sizeof(uint32_t));
+    uint32_t* scol = (uint32_t*)calloc(q->nsel + 1, sizeof(uint32_t));
+    qe_h* srows = (qe_h*)calloc(q->nsel + 1, sizeof(qe_h));
+    int* at = (int*)calloc(q->nsel + 1, sizeof(int));
+    uint64_t total = 1;
+    if (rc == 0 && !zero) {
+        int sat = 0;
+        for (int i = -1; i < P->nc; i++) {
+            if (i < 0 ? !P->agg : !P->C[i].alive) continue;
+            const uint64_t sz = i < 0 ? P->agg_size : P->C[i].size;
+            if (sz == 0) zero = 1;
+            if (__builtin_mul_overflow(total, sz, &total)) sat = 1;
+        }
+        if (sat) total = UINT64_MAX;
+    }
+    if (zero) total = 0;
+    int ns = 0;
+    for (size_t s = 0; rc == 0 && !zero && s < q->nsel; s++) {
+        const int b = (int)q->sel[2 * s];
+        const int ci = P->C[P->comp_of[b]].alive ? P->comp_of[b] : -1;   /* -1: the aggregate last join's */
+        uint64_t m = 1;
+        for (int i = -1; i < P->nc; i++) {
+            if (i == ci || (i < 0 ? !P->agg : !P->C[i].alive)) continue;
+            m *= i < 0 ? P->agg_size : P->C[i].size;
+        }
+        mult[s] = m;
+        if (ci < 0) {
+            sums[s] = P->agg_sums[s];
+            continue;
+        }
+        comp_t* c = &P->C[ci];
+        member* mb = &c->m[member_idx(c, b)];
+        rc = rows_of(P, mb);
+        srel[ns] = mb->vcol ? QE_PLAN_VALUES : q->rels[b];
+        scol[ns] = (uint32_t)q->sel[2 * s + 1];
+        srows[ns] = mb->rows;
+        at[ns++] = (int)s;
+    }
+    if (rc == 0 && ns) {
+        uint64_t* part = (uint64_t*)calloc((size_t)ns, sizeof(uint64_t));
+        rc = e->checksums(e->u, ns, srel, scol, srows, part);
+        for (int k = 0; k < ns; k++) sums[at[k]] = part[k];
+        free(part);
+    }
+    if (rc == 0 && !zero && e->world > 1) rc = e->allreduce(e->u, sums, (int)q->nsel);
+    if (rc == 0) {
+        for (size_t s = 0; s < q->nsel; s++) {
+            if (zero) fputs("NULL ", out);
+            else fprintf(out, "%lu ", (unsigned long)(sums[s] * mult[s]));
+        }
+        fputc('\n', out);
+        if (rows_out) *rows_out = total;
+    }
+    free(sums);
+    free(mult);
+    free(srel);
+    free(scol);
+    free(srows);
+    free(at);
     for (int i = 0; i < P->nc; i++)
         if (P->C[i].alive) free_comp(P, i);
     for (size_t b = 0; b < nb; b++) rel(P, P->list[b]);
@@ -1205,5 +1504,37 @@ int qe_plan_run_text(const qe_engine* e, const char* text, char** out, size_t* o
     qe_free_queries(qs, nq);
     fclose(f);
     if (nrefused) *nrefused = refused;
+    return rc;
+}
+
+int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uint64_t* rows) {
+    /* the query's bytes are buffered: a query that fails prints nothing (the batch's output ends with
+     * the query before it) */
+    char* qbuf = NULL;
+    size_t qlen = 0;
+    FILE* qf = open_memstream(&qbuf, &qlen);
+    if (!qf) return QE_ENOMEM;
+    uint64_t r = 0;
+    const int rc = plan_query_rel(e, (const query_t*)query, qf, &r);
+    fclose(qf);
+    if (rc == 0) {
+        if (qlen) fwrite(qbuf, 1, qlen, (FILE*)out);
+        if (rows) *rows = r;
+    }
+    free(qbuf);
+    return rc;
+}
+
+int qe_plan_run_text_relational(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows) {
+    *out = NULL;
+    *outlen = 0;
+    FILE* f = open_memstream(out, outlen);
+    if (!f) return QE_ENOMEM;
+    size_t nq = 0;
+    query_t* qs = qe_parse_text(text, &nq);     /* parsed before anything runs (main/queries_main.c:31-37) */
+    int rc = 0;
+    for (size_t i = 0; rc == 0 && i < nq; i++) rc = qe_plan_run_query_relational(e, &qs[i], f, rows);
+    qe_free_queries(qs, nq);
+    fclose(f);
     return rc;
 }

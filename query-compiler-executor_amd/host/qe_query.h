@@ -70,6 +70,9 @@ int qe_exec_query(struct qe_ctx* ctx, query_t* q, FILE* out);
 /* csrc/qe_comm.hip: one parsed, arranged query through the partitioned plan on this ctx alone
  * (one rank), the faithful executor for what the plan refuses -- the same bytes */
 int qe_plan_exec_query(struct qe_ctx* ctx, query_t* q, FILE* out);
+/* csrc/qe_comm.hip: one parsed query through the plan's relational mode on this ctx alone (one
+ * rank): the textbook answer, or an error and no output (include/qe_plan.h) */
+int qe_plan_exec_query_relational(struct qe_ctx* ctx, query_t* q, FILE* out);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("QE_LIB_PATH") or os.path.join(PKG, "build", "libqe.so
 HEADER = os.path.join(os.path.dirname(PKG), "include", "qe.h")
 
 QE_EINVAL, QE_EHIP, QE_ENOMEM, QE_EEXIT, QE_ETOOBIG, QE_ENOTSUP = -1, -2, -3, -4, -5, -6
+QE_EXEC_FAITHFUL, QE_EXEC_PLAN, QE_EXEC_RELATIONAL = 0, 1, 2   # qe_run_queries_lanes' executors
 LIST_DISTINCT = 1
 PAIRS_DISTINCT, PAIRS_SORTED = 1, 2
 
@@ -142,6 +143,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "qe_run_queries_local": (I, [P, I, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "qe_workers": (I, [P, I, C.POINTER(C.c_void_p)]),
+        "qe_select_equal": (I, [P, Col, C.POINTER(List), Col, C.POINTER(List), I, C.POINTER(C.POINTER(List)),
+                                C.POINTER(List)]),
+        "qe_select_equal_tile": (C.c_uint32, []),
+        "qe_run_queries_relational": (I, [P, P, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+        "qe_run_queries_relational_local": (I, [P, I, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_uint64)]),
         "qe_bind_thread": (I, [P]),
     }
     for name, (res, args) in sig.items():
@@ -247,17 +254,53 @@ class Ctx:
             raise QEError(rc, self.lib.qe_last_error(self.h).decode())
         return s, (1 if rc == QE_EEXIT else 0)
 
-    def run_lanes(self, text: str, workers: int = 4, plan: bool = True) -> tuple[str, int]:
+    def run_lanes(self, text: str, workers: int = 4, plan: bool = True, executor: int | None = None) -> tuple[str, int]:
         """qe_run_queries_lanes: the batch on `workers` lanes, each query through the partitioned
-        plan (faithful fallback) or the faithful executor -- the same bytes either way"""
+        plan (faithful fallback) or the faithful executor -- the same bytes either way.  executor
+        (overrides plan): QE_EXEC_FAITHFUL / QE_EXEC_PLAN / QE_EXEC_RELATIONAL; the relational mode
+        returns (stdout, code) as run_relational does"""
+        if executor is None:
+            executor = QE_EXEC_PLAN if plan else QE_EXEC_FAITHFUL
         out, n = C.c_void_p(), C.c_size_t()
-        rc = self.lib.qe_run_queries_lanes(self.h, workers, 1 if plan else 0, text.encode(), C.byref(out), C.byref(n))
+        rc = self.lib.qe_run_queries_lanes(self.h, workers, executor, text.encode(), C.byref(out), C.byref(n))
         s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
         if out.value:
             self.lib.qe_free_host(out)
+        if executor == QE_EXEC_RELATIONAL:
+            return s, self._relational_code(rc)
         if rc not in (0, QE_EEXIT):
             raise QEError(rc, self.lib.qe_last_error(self.h).decode())
         return s, (1 if rc == QE_EEXIT else 0)
+
+    def _relational_code(self, rc: int) -> int:
+        """the relational mode's outcomes are codes, not exceptions: 0, or the error that ended the
+        batch after the lines already returned (QE_EINVAL, QE_ENOTSUP, QE_ETOOBIG); anything else
+        is a failure of the library"""
+        if rc not in (0, QE_EINVAL, QE_ENOTSUP, QE_ETOOBIG):
+            raise QEError(rc, self.lib.qe_last_error(self.h).decode())
+        return rc
+
+    def run_relational(self, text: str, comm: "Comm | None" = None) -> tuple[str, int]:
+        """qe_run_queries_relational: one line per query with the textbook (SQL) answer, for every
+        query shape -> (stdout on rank 0, 0 or the code that ended the batch)"""
+        out, n = C.c_void_p(), C.c_size_t()
+        rc = self.lib.qe_run_queries_relational(self.h, comm.h if comm else None, text.encode(), C.byref(out),
+                                                C.byref(n))
+        s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
+        if out.value:
+            self.lib.qe_free_host(out)
+        return s, self._relational_code(rc)
+
+    def run_relational_local(self, text: str, nranks: int) -> tuple[str, int, int]:
+        """qe_run_queries_relational_local: the same on `nranks` in-process ranks of this GPU ->
+        (stdout, 0 or the code that ended the batch, bytes exchanged)"""
+        out, n, sent = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        rc = self.lib.qe_run_queries_relational_local(self.h, nranks, text.encode(), C.byref(out), C.byref(n),
+                                                      C.byref(sent))
+        s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
+        if out.value:
+            self.lib.qe_free_host(out)
+        return s, self._relational_code(rc), sent.value
 
     def sort_cache_stats(self) -> tuple[int, int]:
         """(cached base-column sorts reused, built) over this ctx's finished batches"""
@@ -347,6 +390,19 @@ class Ctx:
         l = List()
         self._chk(self.lib.qe_filter_scan(self.h, col, op.encode(), v, C.byref(l)))
         return l
+
+    def select_equal(self, colA: Col, a: List | None, colB: Col, b: List | None, lists: list[List]) -> list[List]:
+        """qe_select_equal: the positions i with colA[a[i]] == colB[b[i]] (None: row i) of every
+        list of `lists` (aligned with a and b), order preserved -> new lists"""
+        n = len(lists)
+        inp = (C.POINTER(List) * n)(*[C.pointer(l) for l in lists])
+        outs = (List * n)()
+        self._chk(self.lib.qe_select_equal(self.h, colA, C.byref(a) if a is not None else None, colB,
+                                           C.byref(b) if b is not None else None, n, inp, outs))
+        return [outs[i] for i in range(n)]
+
+    def select_equal_tile(self) -> int:
+        return int(self.lib.qe_select_equal_tile())
 
     def filter_refine(self, col: Col, op: str, v: int, l: List) -> List:
         self._chk(self.lib.qe_filter_refine(self.h, col, op.encode(), v, C.byref(l)))
