@@ -140,6 +140,9 @@ int  qe_run_queries_parallel(qe_ctx*, int workers, const char* text, char** out,
  * below) on its lane's ctx as one rank -- the textbook answer, no fallback; the first failing query
  * ends the batch with the output of the queries before it */
 #define QE_EXEC_RELATIONAL 2
+/* QE_EXEC_THETA: the same through the plan's theta mode (qe_run_queries_theta below): a written
+ * column < / > column predicate is honoured instead of refused */
+#define QE_EXEC_THETA 3
 int  qe_run_queries_lanes(qe_ctx*, int workers, int executor, const char* text, char** out, size_t* outlen);
 /* A batch's shared sorts of whole base columns (no reference counterpart: the reference sorts a
  * base relation again for every join, src/join.c:122-142 + :5-94).  on = 1: from now on the first
@@ -175,6 +178,13 @@ int qe_select_equal(qe_ctx*, qe_col colA, const qe_list* a, qe_col colB, const q
                     const qe_list* const* in, qe_list* outs);
 /* elements per tile of qe_select_equal's compaction (its tests size their inputs around it) */
 uint32_t qe_select_equal_tile(void);
+/* qe_select_equal with the written operator: keep positions i with colA[a[i]] op colB[b[i]], op one
+ * of '=', '<', '>' (unsigned 64-bit, strict; anything else: QE_EINVAL).  The same contract, pipeline
+ * and tile; '=' is qe_select_equal itself (stage select_equal), '<' and '>' report as stage
+ * select_compare.  No reference counterpart: the theta mode's selection inside a component
+ * (include/qe_plan.h select_cmp). */
+int qe_select_compare(qe_ctx*, qe_col colA, const qe_list* a, char op, qe_col colB, const qe_list* b, int nl,
+                      const qe_list* const* in, qe_list* outs);
 /* a3/a4: allocate_relation / allocate_relation_mid_results (src/join.c:96-142):
  * (key = col[rowid], rowid) for rows == NULL (every row) or for each rowid of *rows in order. */
 int qe_gather_pairs(qe_ctx*, qe_col col, const qe_list* rows, qe_pairs* out);
@@ -231,6 +241,14 @@ int qe_checksums(qe_ctx*, int n, const qe_col* cols, const qe_list* const* rows,
  * qe_checksum over the list qe_merge_join would have produced for that side
  * (sum_pairs col(pR) = sum_k (sum_{r in R_k} col(r)) * |S_k|). */
 int qe_checksum_weighted(qe_ctx*, qe_col col, const qe_pairs* p, uint64_t* sum);
+/* Theta mode's link (no reference counterpart): R->match[i] = #{j : R.key[i] op
+ * S.key[j]} for op '<' or '>' (unsigned, strict), *pairs = their sum.  Both sides must carry
+ * QE_PAIRS_SORTED (QE_EINVAL otherwise) and hold fewer than 2^32 keys (QE_ETOOBIG).  match is
+ * allocated as qe_merge_join_counts does; QE_PAIRS_MATCHED is cleared on R, not set: these are no
+ * equi-join's counts.  qe_checksum_weighted then sums col[val[i]] * match[i].  One pass over R in
+ * tiles of 4096 keys: two searches bound the tile's window of S, each key finds its bound inside
+ * the window -- staged in LDS when it fits, read from global memory when it does not. */
+int qe_theta_counts(qe_ctx*, qe_pairs* R, const qe_pairs* S, char op, uint64_t* pairs);
 /* a8 + print_sums, aggregate form for two BASE columns (C5: the query's last join, each side's
  * selects on at most one column): with c_i = #S rows whose key equals R.key[i] (and symmetric),
  * out[0] = sum_i c_i = the join's pair count P, out[1] = sum_i valR[i] * c_i and out[2] =
@@ -316,6 +334,15 @@ int  qe_run_queries_dist(qe_ctx*, qe_comm*, const char* text, char** out, size_t
  * No fallback executor: QE_EINVAL / QE_ENOTSUP / QE_ETOOBIG end the batch with the output of the
  * queries before.  qe_last_result_rows: the product of the component sizes, saturated. */
 int  qe_run_queries_relational(qe_ctx*, qe_comm*, const char* text, char** out, size_t* outlen);
+/* Theta mode (include/qe_plan.h qe_plan_run_text_theta): the relational mode
+ * with a written column < / > column predicate honoured -- a filter, a selection inside a component
+ * or a link between two components; a query without one prints the relational mode's line.
+ * QE_ENOTSUP: a component with two or more links; QE_ETOOBIG: a link side of 2^32 rows or more. */
+int  qe_run_queries_theta(qe_ctx*, qe_comm*, const char* text, char** out, size_t* outlen);
+/* Concatenate every rank's device array d[0..n) in rank order into *out (a new device buffer of
+ * *out_n words, at least one allocated; release with qe_buffer_free).  The counts differ per rank
+ * and may be 0.  comm == NULL or one rank: a copy.  Every rank of the communicator calls it. */
+int  qe_allgather_u64(qe_ctx*, qe_comm*, const uint64_t* d, uint64_t n, uint64_t** out, uint64_t* out_n);
 /* The in-process transport: nranks communicators over ctxs[0..nranks) (contexts of this process --
  * typically qe_workers of one ctx on ONE GPU, where RCCL refuses a second rank), each rank driven by
  * its own host thread.  Only the transport differs from qe_comm_init's: the counts all-to-all and the
@@ -334,6 +361,9 @@ int  qe_run_queries_local(qe_ctx*, int nranks, const char* text, char** out, siz
 /* qe_run_queries_relational on nranks (1..16) in-process ranks, as qe_run_queries_local */
 int  qe_run_queries_relational_local(qe_ctx*, int nranks, const char* text, char** out, size_t* outlen,
                                      uint64_t* bytes_sent);
+/* qe_run_queries_theta on nranks (1..16) in-process ranks, as qe_run_queries_local */
+int  qe_run_queries_theta_local(qe_ctx*, int nranks, const char* text, char** out, size_t* outlen,
+                                uint64_t* bytes_sent);
 
 /* The ctx's HIP stream (hipStream_t), for callers that order their own work against it. */
 int qe_sync_stream_ptr(qe_ctx*, void** stream);

@@ -141,6 +141,22 @@ typedef struct qe_engine {
      * Rank-local: a component's lists are aligned per rank, so nothing is exchanged. */
     int (*select_eq)(void* u, uint32_t rel_a, uint32_t col_a, qe_h a, uint32_t rel_b, uint32_t col_b, qe_h b, int n,
                      const qe_h* lists, qe_h* outs);
+    /* THETA MODE ONLY (the _theta entry points below; no other entry point reads these four, and the
+     * theta entry points return QE_EINVAL when one is missing).
+     * select_eq with the written operator: keep the positions i with col_a[a[i]] op col_b[b[i]],
+     * op one of '=', '<', '>' (unsigned 64-bit, strict) */
+    int (*select_cmp)(void* u, uint32_t rel_a, uint32_t col_a, qe_h a, char op, uint32_t rel_b, uint32_t col_b, qe_h b,
+                      int n, const qe_h* lists, qe_h* outs);
+    /* *all = every rank's `keys` (uint64, borrowed) concatenated in rank order; the lengths differ
+     * per rank and may be 0.  Never called at world 1. */
+    int (*allgather)(void* u, qe_h keys, qe_h* all);
+    /* *w (uint32, aligned with qk): w[i] = #{j : qk[i] op sk[j]}, op '<' or '>'; *pairs = sum of w.
+     * qk and sk (uint64 keys, sk in any order) are borrowed.  QE_ETOOBIG: a side of 2^32 keys or more. */
+    int (*theta_weights)(void* u, qe_h qk, qe_h sk, char op, qe_h* w, uint64_t* pairs);
+    /* checksums with a weight per row: sums[k] = sum of col_k[rows_k[i]] * w_k[i] mod 2^64
+     * (everything borrowed; rels[k] is never QE_PLAN_VALUES) */
+    int (*checksums_weighted)(void* u, int n, const uint32_t* rels, const uint32_t* cols, const qe_h* rows,
+                              const qe_h* w, uint64_t* sums);
 } qe_engine;
 
 /* Replay the reference's variant choice and list bookkeeping for every query of `text` on the
@@ -177,6 +193,23 @@ int qe_plan_run_query(const qe_engine* e, void* query, void* out, uint64_t* rows
  * order of the predicates). */
 int qe_plan_run_text_relational(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows);
 int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uint64_t* rows);
+
+/* Theta mode: the relational mode with a written column < / > column predicate honoured
+ * (DESIGN.md §10); a query without one prints what the relational mode prints.  Comparisons are
+ * unsigned 64-bit and strict.  b.x op b.y (one binding) is a filter on b's rows.  Two bindings that
+ * the query's column = column predicates connect (union-find, whatever the join order): a selection
+ * inside their component (e->select_cmp), run as soon as both share it.  Two bindings nothing
+ * connects: a theta link between two components A and B, applied after every join and selection and
+ * never materialised -- the pair counts as one component of size P = #{(i, j) : kA_i op kB_j}, a
+ * select of a binding of A prints sum_i v_i * #{j : kA_i op kB_j} (B alike) times the sizes of the
+ * other components mod 2^64, every select is NULL when P == 0, and *rows uses P for the pair.  At N
+ * ranks every rank gathers both sides' keys (e->allgather), 8 bytes per row.
+ * QE_ENOTSUP (qe_plan_why names the reason; decided on the text alone, before any collective): a
+ * component with two or more links -- a chain A < B < C, or two predicates between the same two
+ * otherwise unconnected components (a band).  QE_ETOOBIG: a link side of 2^32 rows or more over all
+ * ranks (the per-row counts are uint32).  QE_EINVAL: an engine without the four theta callbacks. */
+int qe_plan_run_text_theta(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows);
+int qe_plan_run_query_theta(const qe_engine* e, void* query, void* out, uint64_t* rows);
 
 #ifdef __cplusplus
 }

@@ -905,6 +905,123 @@ int e_select_eq(void* u, uint32_t rel_a, uint32_t col_a, qe_h a, uint32_t rel_b,
     });
 }
 
+// ---- theta mode (include/qe_plan.h: the _theta entry points alone read these four) --------------
+int e_select_cmp(void* u, uint32_t rel_a, uint32_t col_a, qe_h a, char op, uint32_t rel_b, uint32_t col_b, qe_h b, int n,
+                 const qe_h* lists, qe_h* outs) {
+    Eng* e = E(u);
+    return guard(e, [&] {
+        qe_ctx* c = e->c;
+        if (n < 1 || n > 64) throw Error(QE_EINVAL, "select_cmp: 1..64 lists");
+        const qe_list la = as_list(A(a)), lb = as_list(A(b));
+        std::vector<qe_list> in(n), out(n);
+        std::vector<const qe_list*> inp(n);
+        for (int i = 0; i < n; i++) {
+            in[i] = as_list(A(lists[i]));
+            inp[i] = &in[i];
+        }
+        ck(qe_select_compare(c, column(c, rel_a, col_a), &la, op, column(c, rel_b, col_b), a == b ? &la : &lb, n,
+                             inp.data(), out.data()), c);
+        for (int i = 0; i < n; i++) outs[i] = H(new_arr(c, out[i].d, out[i].n, false));
+    });
+}
+
+// a device block that a throw frees
+struct DBuf {
+    qe_ctx* c;
+    void* p;
+    DBuf(qe_ctx* cc, void* pp) : c(cc), p(pp) {}
+    DBuf(const DBuf&) = delete;
+    DBuf& operator=(const DBuf&) = delete;
+    ~DBuf() {
+        if (p) dfree(c, p);
+    }
+    void* release() {
+        void* r = p;
+        p = nullptr;
+        return r;
+    }
+};
+
+// a key array as the plan's `keys` made it: complete (a gather may have left it as u32 until read)
+const uint64_t* complete_keys(qe_ctx* c, const DArr* k) {
+    qe_pairs v{};
+    v.key = static_cast<uint64_t*>(k->d);
+    v.n = k->n;
+    pairs_need_keys(c, &v);
+    return v.key;
+}
+
+int e_allgather(void* u, qe_h keys, qe_h* all) {
+    Eng* e = E(u);
+    return guard(e, [&] {
+        qe_ctx* c = e->c;
+        const DArr* k = A(keys);
+        uint64_t* out = nullptr;
+        uint64_t n = 0;
+        ck(qe_allgather_u64(c, e->comm, complete_keys(c, k), k->n, &out, &n), c);
+        *all = H(new_arr(c, out, n, true));
+    });
+}
+
+// w[i] = #{j : qk[i] op sk[j]}: qk sorted with its positions, sk sorted alone, one qe_theta_counts
+// pass whose store scatters each count back to its key's position
+int e_theta_weights(void* u, qe_h qk, qe_h sk, char op, qe_h* w, uint64_t* pairs) {
+    Eng* e = E(u);
+    return guard(e, [&] {
+        qe_ctx* c = e->c;
+        const DArr *q = A(qk), *s = A(sk);
+        if (op != '<' && op != '>') throw Error(QE_EINVAL, "theta_weights: the operator is < or >");
+        if ((q->n >> 32) || (s->n >> 32)) throw Error(QE_ETOOBIG, "theta_weights: a side of 2^32 keys or more");
+        DBuf wd(c, dalloc_t<uint32_t>(c, std::max<uint64_t>(q->n, 1)));
+        if (q->n == 0 || s->n == 0) {          // nothing to compare with: every count is 0
+            if (q->n) QE_HIP(hipMemsetAsync(wd.p, 0, q->n * 4, c->stream));
+            *pairs = 0;
+            *w = H(new_arr(c, wd.release(), q->n, false));
+            return;
+        }
+        qe_pairs R = side_pairs(q, nullptr);   // (val null: the positions ride through the sort)
+        qe_pairs S{};
+        complete_keys(c, s);
+        void* skeys = nullptr;                 // S's sorted keys when the sort made a new buffer
+        try {
+            ck(qe_sort_pairs(c, &R), c);
+            const uint64_t sbits[2] = {s->kor, s->kand};
+            const SortOut so = radix_sort_u64(c, static_cast<const uint64_t*>(s->d), nullptr, s->n, false,
+                                              s->bits ? sbits : nullptr);
+            if (so.keys_new) skeys = so.keys;
+            S.key = static_cast<uint64_t*>(so.keys);
+            S.n = s->n;
+            S.flags = QE_PAIRS_SORTED;
+            pairs_need_keys(c, &R);
+            *pairs = theta_counts(c, &R, &S, op, static_cast<uint32_t*>(wd.p), q->n);
+        } catch (...) {
+            if (skeys) dfree(c, skeys);
+            qe_pairs_free(c, &R);
+            throw;
+        }
+        if (skeys) dfree(c, skeys);
+        qe_pairs_free(c, &R);
+        *w = H(new_arr(c, wd.release(), q->n, false));
+    });
+}
+
+int e_checksums_weighted(void* u, int n, const uint32_t* rels, const uint32_t* cols, const qe_h* rows, const qe_h* w,
+                         uint64_t* sums) {
+    Eng* e = E(u);
+    return guard(e, [&] {
+        qe_ctx* c = e->c;
+        for (int i = 0; i < n; i++) {
+            const DArr *r = A(rows[i]), *wt = A(w[i]);
+            if (rels[i] == QE_PLAN_VALUES || r->n != wt->n) throw Error(QE_EINVAL, "checksums_weighted: rowids and weights of one length");
+            qe_pairs p{};                      // the view qe_checksum_weighted reads: {val, match}
+            p.val = static_cast<uint32_t*>(r->d);
+            p.match = static_cast<uint32_t*>(wt->d);
+            p.n = r->n;
+            ck(qe_checksum_weighted(c, column(c, rels[i], cols[i]), &p, &sums[i]), c);
+        }
+    });
+}
+
 int e_length(void* u, qe_h h, uint64_t* n) {
     (void)u;
     *n = A(h)->n;
@@ -1172,6 +1289,10 @@ qe_engine make_engine(Eng* e) {
         g.keys_of = e_keys_of;
     }
     g.select_eq = e_select_eq;
+    g.select_cmp = e_select_cmp;
+    g.allgather = e_allgather;
+    g.theta_weights = e_theta_weights;
+    g.checksums_weighted = e_checksums_weighted;
     return g;
 }
 
@@ -1252,8 +1373,9 @@ int qe_comm_init_local(qe_ctx* const* ctxs, int nranks, qe_comm** out) {
     QE_API_END(c0)
 }
 
-// qe_run_queries_local (relational = false) and qe_run_queries_relational_local over the same ranks
-static int run_local(qe_ctx* c, int nranks, bool relational, const char* text, char** out, size_t* outlen,
+// qe_run_queries_local (mode 0), qe_run_queries_relational_local (1) and qe_run_queries_theta_local (2)
+// over the same ranks
+static int run_local(qe_ctx* c, int nranks, int mode, const char* text, char** out, size_t* outlen,
                      uint64_t* refused, uint64_t* bytes_sent) {
     QE_API_BEGIN(c)
     *out = nullptr;
@@ -1276,8 +1398,10 @@ static int run_local(qe_ctx* c, int nranks, bool relational, const char* text, c
     for (int r = 0; r < nranks; r++)
         th.emplace_back([&, r] {
             qe_bind_thread(w[r]);
-            rcs[r] = relational ? qe_run_queries_relational(w[r], m[r], text, &outs[r], &lens[r])
-                                : qe_run_queries_dist(w[r], m[r], text, &outs[r], &lens[r], &ref[r]);
+            const bool relational = mode != 0;
+            rcs[r] = mode == 2   ? qe_run_queries_theta(w[r], m[r], text, &outs[r], &lens[r])
+                     : mode == 1 ? qe_run_queries_relational(w[r], m[r], text, &outs[r], &lens[r])
+                                 : qe_run_queries_dist(w[r], m[r], text, &outs[r], &lens[r], &ref[r]);
             // never leave a peer waiting -- but the codes that end a relational batch are every rank's
             // (decided on the text alone, or all-reduced by the plan): a rank that leaves with one must
             // not break the group while a peer is still inside the previous query's last collective
@@ -1314,12 +1438,17 @@ static int run_local(qe_ctx* c, int nranks, bool relational, const char* text, c
 
 int qe_run_queries_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen, uint64_t* refused,
                          uint64_t* bytes_sent) {
-    return run_local(c, nranks, false, text, out, outlen, refused, bytes_sent);
+    return run_local(c, nranks, 0, text, out, outlen, refused, bytes_sent);
 }
 
 int qe_run_queries_relational_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen,
                                     uint64_t* bytes_sent) {
-    return run_local(c, nranks, true, text, out, outlen, nullptr, bytes_sent);
+    return run_local(c, nranks, 1, text, out, outlen, nullptr, bytes_sent);
+}
+
+int qe_run_queries_theta_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen,
+                               uint64_t* bytes_sent) {
+    return run_local(c, nranks, 2, text, out, outlen, nullptr, bytes_sent);
 }
 
 void qe_comm_fini(qe_comm* m) {
@@ -1372,6 +1501,79 @@ int qe_allreduce_u64(qe_ctx* c, qe_comm* m, uint64_t* vals, int n) {
     QE_HIP(hipMemcpyAsync(m->h_red, m->d_red, n * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
     QE_HIP(hipStreamSynchronize(m->stream));
     std::memcpy(vals, m->h_red, n * sizeof(uint64_t));
+    return 0;
+    QE_API_END(c)
+}
+
+int qe_allgather_u64(qe_ctx* c, qe_comm* m, const uint64_t* d, uint64_t n, uint64_t** out, uint64_t* out_n) {
+    QE_API_BEGIN(c)
+    if (!out || !out_n || (n && !d)) throw Error(QE_EINVAL, "qe_allgather_u64: bad arguments");
+    *out = nullptr;
+    *out_n = 0;
+    const int W = m ? m->nranks : 1;
+    if (W > 64) throw Error(QE_EINVAL, "qe_allgather_u64: at most 64 ranks");
+    if (W == 1) {   // a copy, on the ctx stream
+        DBuf o(c, dalloc_t<uint64_t>(c, std::max<uint64_t>(n, 1)));
+        if (n) QE_HIP(hipMemcpyAsync(o.p, d, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        *out = static_cast<uint64_t*>(o.release());
+        *out_n = n;
+        return 0;
+    }
+    // the array was made on the ctx stream; the transport works on the communicator's
+    hipEvent_t ready;
+    QE_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    hipError_t er = hipEventRecord(ready, c->stream);
+    if (er == hipSuccess) er = hipStreamWaitEvent(m->stream, ready, 0);
+    (void)hipEventDestroy(ready);
+    QE_HIP(er);
+    uint64_t cnt[64], off[64], total = 0;
+    if (LocalGroup* g = m->local) {   // post the pointer and the count, pull every rank's array
+        try {
+            QE_HIP(hipStreamSynchronize(m->stream));   // (the posted array is complete)
+            g->cnt[m->rank][0] = n;
+            g->keys[m->rank] = d;
+            g->barrier();
+            for (int p = 0; p < W; p++) {
+                cnt[p] = g->cnt[p][0];
+                off[p] = total;
+                total += cnt[p];
+            }
+            DBuf o(c, dalloc_t<uint64_t>(c, std::max<uint64_t>(total, 1)));
+            for (int p = 0; p < W; p++)
+                if (cnt[p])
+                    QE_HIP(hipMemcpyAsync(static_cast<uint64_t*>(o.p) + off[p], g->keys[p], cnt[p] * 8,
+                                          hipMemcpyDeviceToDevice, m->stream));
+            QE_HIP(hipStreamSynchronize(m->stream));
+            g->barrier();                              // every peer has pulled: the posted arrays may be freed
+            *out = static_cast<uint64_t*>(o.release());
+        } catch (...) {
+            g->fail();
+            throw;
+        }
+    } else {   // the counts through the communicator's stream, then one grouped send/recv
+        std::memset(m->h_red, 0, 64 * sizeof(uint64_t));
+        m->h_red[m->rank] = n;
+        QE_HIP(hipMemcpyAsync(m->d_red, m->h_red, W * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+        QE_NCCL(ncclAllGather(m->d_red + m->rank, m->d_red, 1, ncclUint64, m->comm, m->stream));
+        QE_HIP(hipMemcpyAsync(m->h_red, m->d_red, W * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
+        QE_HIP(hipStreamSynchronize(m->stream));       // the one host round trip: receive sizes
+        for (int p = 0; p < W; p++) {
+            cnt[p] = m->h_red[p];
+            off[p] = total;
+            total += cnt[p];
+        }
+        DBuf o(c, dalloc_t<uint64_t>(c, std::max<uint64_t>(total, 1)));
+        QE_NCCL(ncclGroupStart());
+        for (int p = 0; p < W; p++) {
+            QE_NCCL(ncclSend(d, n, ncclUint64, p, m->comm, m->stream));
+            QE_NCCL(ncclRecv(static_cast<uint64_t*>(o.p) + off[p], cnt[p], ncclUint64, p, m->comm, m->stream));
+        }
+        QE_NCCL(ncclGroupEnd());
+        QE_HIP(hipStreamSynchronize(m->stream));       // (the caller reads the result on its own stream)
+        *out = static_cast<uint64_t*>(o.release());
+    }
+    *out_n = total;
+    m->bytes_sent += n * 8 * (uint64_t)(W - 1);
     return 0;
     QE_API_END(c)
 }
@@ -1440,6 +1642,26 @@ int qe_run_queries_relational(qe_ctx* c, qe_comm* m, const char* text, char** ou
     uint64_t rows = c->last_result_rows;
     const int rc = qe_plan_run_text_relational(&g, text, out, outlen, &rows);
     if (rc != 0 && qe_plan_why()[0]) c->err = qe_plan_why();   // (a query refused before it ran)
+    c->last_result_rows = rows;
+    return rc;
+}
+
+int qe_run_queries_theta(qe_ctx* c, qe_comm* m, const char* text, char** out, size_t* outlen) {
+    if (!c) return QE_EINVAL;
+    Eng e{c, m, m ? m->nranks : 1, m ? m->rank : 0, 0};
+    qe_engine g = make_engine(&e);
+    uint64_t rows = c->last_result_rows;
+    const int rc = qe_plan_run_text_theta(&g, text, out, outlen, &rows);
+    if (rc != 0 && qe_plan_why()[0]) c->err = qe_plan_why();   // (a query refused before it ran)
+    c->last_result_rows = rows;
+    return rc;
+}
+
+int qe_plan_exec_query_theta(qe_ctx* c, query_t* q, FILE* out) {
+    Eng e{c, nullptr, 1, 0, 0};
+    qe_engine g = make_engine(&e);
+    uint64_t rows = c->last_result_rows;
+    const int rc = qe_plan_run_query_theta(&g, q, out, &rows);
     c->last_result_rows = rows;
     return rc;
 }

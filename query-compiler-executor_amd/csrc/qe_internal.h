@@ -334,6 +334,9 @@ SortOut radix_sort_u64(qe_ctx* c, const uint64_t* keys, const uint32_t* vals /*n
 // drop one whose pairs are freed; the unordered per-bucket join of two deferred sides (false:
 // not applicable -- the caller completes both sorts and merges as usual)
 void pairs_need_keys(qe_ctx* c, const qe_pairs* p);
+// theta mode (qe_join.hip): R->match[i] = #{j : R.key[i] op S.key[j]} (op '<' or '>', both sides
+// sorted and below 2^32 keys), scattered to w[R.val[i]] (w nullable, wn entries); returns the sum
+uint64_t theta_counts(qe_ctx* c, qe_pairs* R, const qe_pairs* S, char op, uint32_t* w, uint64_t wn);
 void pairs_need_vals(qe_ctx* c, const qe_pairs* p);
 // (also drops a gathered histogram; keep_k32: a key buffer the pairs only borrow keeps its u32
 // keys, PreHist::k32, for another sort of it -- its owner's release frees them)

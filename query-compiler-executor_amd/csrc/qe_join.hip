@@ -1439,6 +1439,116 @@ uint64_t merge_count_side(qe_ctx* c, qe_pairs* A, const qe_pairs* B) {
     return P;
 }
 
+// ---- theta_counts (theta mode) ----------------------------------------------------
+// match[i] = #{j : rk[i] op sk[j]} for sorted rk and sk: with p = upper_bound(sk, rk[i]) the keys
+// above rk[i] are the nS - p behind it ('<'); with p = lower_bound(sk, rk[i]) the keys below it are
+// the p before it ('>').  One workgroup per R tile of MJ_TILE keys; mj_partition's window [wlo, whi)
+// = [lower_bound(first key), upper_bound(last key)) holds both bounds of every key of the tile, so
+// each element searches the window only: staged in LDS when it has at most TH_WIN keys, read from
+// global memory otherwise (heavy duplicates make a window as wide as all of S).  w (nullable): the
+// counts scattered back to the order the pairs were sorted from, w[val[i]] = match[i] (val null:
+// position i), for val[i] < wn.  The tile's counts are summed into *total.
+constexpr int TH_WIN = 6144;   // 48 KiB of LDS: three workgroups per CU
+
+template <bool LESS>
+__global__ void __launch_bounds__(MJB) theta_counts_kernel(const uint64_t* __restrict__ rk,
+                                                           const uint32_t* __restrict__ rv, uint64_t nR,
+                                                           const uint64_t* __restrict__ sk, uint64_t nS,
+                                                           const uint64_t* __restrict__ win,
+                                                           uint32_t* __restrict__ match, uint32_t* __restrict__ w,
+                                                           uint64_t wn, unsigned long long* __restrict__ total) {
+    __shared__ uint64_t s_win[TH_WIN];
+    __shared__ uint64_t red[MJB / 64];
+    const uint32_t tile = blockIdx.x;
+    const uint64_t base = (uint64_t)tile * MJ_TILE;
+    const uint32_t tn = (uint32_t)std::min<uint64_t>(MJ_TILE, nR - base);
+    const uint64_t wlo = win[2 * tile], whi = win[2 * tile + 1];
+    const uint64_t wl = whi - wlo;
+    const bool staged = wl <= (uint64_t)TH_WIN;   // (workgroup-uniform)
+    if (staged) {
+        for (uint32_t j = threadIdx.x; j < (uint32_t)wl; j += MJB) s_win[j] = sk[wlo + j];
+        __syncthreads();
+    }
+    uint64_t sum = 0;
+    for (uint32_t e = threadIdx.x; e < tn; e += MJB) {
+        const uint64_t key = rk[base + e];
+        uint64_t p;
+        if (staged) {
+            auto at = [&](uint64_t j) { return s_win[j]; };
+            p = wlo + (LESS ? upper_bound_f(0, wl, key, at) : lower_bound_f(0, wl, key, at));
+        } else {
+            auto at = [&](uint64_t j) { return sk[j]; };
+            p = LESS ? upper_bound_f(wlo, whi, key, at) : lower_bound_f(wlo, whi, key, at);
+        }
+        const uint32_t cnt = (uint32_t)(LESS ? nS - p : p);   // (nS < 2^32: checked by the caller)
+        match[base + e] = cnt;
+        if (w) {
+            const uint64_t pos = rv ? (uint64_t)rv[base + e] : base + e;
+            if (pos < wn) w[pos] = cnt;
+        }
+        sum += cnt;
+    }
+    sum = wave_sum_u64(sum);
+    if (lane_id() == 0) red[wave_id()] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (int k = 0; k < MJB / 64; k++) t += red[k];
+        if (t) atomicAdd(total, (unsigned long long)t);
+    }
+}
+
+// R->match (allocated as merge_count_side does) and, when w is given, the scatter; returns the sum
+// of the counts.  Both sides sorted, keys complete, nR and nS below 2^32 (the caller checks).
+// -DQE_THETA_PLAIN (measurement only): no windows, every element searches all of S
+// in global memory -- the baseline the windowed kernel is compared with.
+uint64_t theta_counts_impl(qe_ctx* c, qe_pairs* R, const qe_pairs* S, char op, uint32_t* w, uint64_t wn) {
+    const uint64_t nR = R->n, nS = S->n;
+    if (!R->match && nR) {
+        R->match = dalloc_t<uint32_t>(c, nR);
+        R->owns |= 4;
+    }
+    if (nR == 0) return 0;
+    if (nS == 0) {
+        QE_HIP(hipMemsetAsync(R->match, 0, nR * 4, c->stream));
+        if (w && wn) QE_HIP(hipMemsetAsync(w, 0, wn * 4, c->stream));
+        return 0;
+    }
+    const uint32_t nt = (uint32_t)((nR + MJ_TILE - 1) / MJ_TILE);
+    uint64_t* win = dalloc_t<uint64_t>(c, 2 * (uint64_t)nt + 1);
+    unsigned long long* total = (unsigned long long*)(win + 2 * (uint64_t)nt);
+    uint64_t P = 0;
+    try {
+#ifdef QE_THETA_PLAIN
+        std::vector<uint64_t> all(2 * (size_t)nt + 1, 0);
+        for (uint32_t k = 0; k < nt; k++) all[2 * k + 1] = nS;
+        QE_HIP(hipMemcpyAsync(win, all.data(), all.size() * 8, hipMemcpyHostToDevice, c->stream));
+        QE_HIP(hipStreamSynchronize(c->stream));
+#endif
+        {
+            Timed t(c, "theta_counts", 8.0 * nR + 8.0 * nS + 4.0 * nR);
+#ifndef QE_THETA_PLAIN
+            hipLaunchKernelGGL(mj_partition, dim3((nt + 3) / 4), dim3(256), 0, c->stream, R->key, nR, S->key, nS, nt,
+                               win, (uint64_t*)total, nullptr);
+            QE_HIP(hipGetLastError());
+#endif
+            if (op == '<')
+                hipLaunchKernelGGL(theta_counts_kernel<true>, dim3(nt), dim3(MJB), 0, c->stream, R->key, R->val, nR,
+                                   S->key, nS, win, R->match, w, wn, total);
+            else
+                hipLaunchKernelGGL(theta_counts_kernel<false>, dim3(nt), dim3(MJB), 0, c->stream, R->key, R->val, nR,
+                                   S->key, nS, win, R->match, w, wn, total);
+            QE_HIP(hipGetLastError());
+        }
+        P = read_u64(c, (const uint64_t*)total);
+    } catch (...) {
+        dfree(c, win);
+        throw;
+    }
+    dfree(c, win);
+    return P;
+}
+
 static void prefix_max(qe_ctx* c, const uint64_t* x, uint64_t n, uint64_t* out) {
     const uint64_t nb = (n + PM_CHUNK - 1) / PM_CHUNK;
     uint64_t* bmax = dalloc_t<uint64_t>(c, std::max<uint64_t>(nb, 1));
@@ -1973,6 +2083,10 @@ bool join_pairs_sums(qe_ctx* c, qe_pairs* R, qe_pairs* S, const uint32_t* xa, co
     *S = S0;
     return false;
 }
+
+uint64_t theta_counts(qe_ctx* c, qe_pairs* R, const qe_pairs* S, char op, uint32_t* w, uint64_t wn) {
+    return theta_counts_impl(c, R, S, op, w, wn);
+}
 }  // namespace qe
 
 extern "C" {
@@ -2035,6 +2149,19 @@ int qe_merge_join_counts(qe_ctx* c, qe_pairs* R, qe_pairs* S, uint64_t* pairs) {
     R->flags |= QE_PAIRS_MATCHED;
     S->flags |= QE_PAIRS_MATCHED;
     *pairs = Q;
+    return 0;
+    QE_API_END(c)
+}
+
+int qe_theta_counts(qe_ctx* c, qe_pairs* R, const qe_pairs* S, char op, uint64_t* pairs) {
+    QE_API_BEGIN(c)
+    if (op != '<' && op != '>') throw Error(QE_EINVAL, "qe_theta_counts: the operator is < or >");
+    if (!(R->flags & PF_SORTED) || !(S->flags & PF_SORTED)) throw Error(QE_EINVAL, "qe_theta_counts needs sorted inputs");
+    if ((R->n >> 32) || (S->n >> 32)) throw Error(QE_ETOOBIG, "qe_theta_counts: a side of 2^32 keys or more");
+    pairs_need_keys(c, R);
+    pairs_need_keys(c, S);
+    R->flags &= ~QE_PAIRS_MATCHED;   // (match is no equi-join's count: qe_merge_join_counts must not reuse it)
+    *pairs = theta_counts(c, R, S, op, nullptr, 0);
     return 0;
     QE_API_END(c)
 }

@@ -206,7 +206,10 @@ __device__ __forceinline__ void load4_u32(const uint32_t* p, uint64_t base, uint
 // low words is then the comparison).  A rowid past its column never matches (no read past the
 // column).  keep (nullable): the kept flags of positions base..base+3 as one byte per thread step,
 // for the launches that carry a wider component's further lists (KeepCarryOp) without gathering again.
-struct SelectEqualOp {
+// CMP: the comparison of the two gathered values (OP_EQ: qe_select_equal; OP_LT / OP_GT: the theta
+// mode's qe_select_compare -- unsigned, strict)
+template <int CMP>
+struct SelectCompareOp {
     static constexpr int VEC = 4;
     const uint64_t *ca, *cb;
     const uint32_t *ca32, *cb32;   // both set, or both null
@@ -250,7 +253,7 @@ struct SelectEqualOp {
         for (int k = 0; k < 4; k++) {
             const bool ok = base + k < n && ra[k] < na && rb[k] < nb;
             bool eq = false;
-            if (ok) eq = ca32 ? ca32[ra[k]] == cb32[rb[k]] : ca[ra[k]] == cb[rb[k]];
+            if (ok) eq = ca32 ? cmp_op<CMP>(ca32[ra[k]], cb32[rb[k]]) : cmp_op<CMP>(ca[ra[k]], cb[rb[k]]);
             f[k] = eq;
             bits |= (uint32_t)eq << k;
         }
@@ -258,7 +261,9 @@ struct SelectEqualOp {
     }
 };
 
-struct KeepCarryOp {            // two more lists of the component, by SelectEqualOp's kept flags
+using SelectEqualOp = SelectCompareOp<OP_EQ>;
+
+struct KeepCarryOp {            // two more lists of the component, by SelectCompareOp's kept flags
     static constexpr int VEC = 4;
     const uint8_t* keep;
     const uint32_t *in0, *in1;  // in1 null when the launch carries one list
@@ -861,10 +866,13 @@ uint64_t compact_prefix_max_hits(qe_ctx* c, const uint64_t* key, const uint64_t*
 constexpr int SE_ITEMS = QE_SE_ITEMS;
 constexpr uint32_t SE_TILE = CB * SE_ITEMS * SelectEqualOp::VEC;
 
-// outs[0..nl): dalloc blocks of n entries; returns the survivors' count
-static uint64_t select_equal(qe_ctx* c, qe_col colA, const uint32_t* a, qe_col colB, const uint32_t* b, uint64_t n,
-                             int nl, const uint32_t* const* in, uint32_t* const* outs) {
+// outs[0..nl): dalloc blocks of n entries; returns the survivors' count.  CMP = OP_EQ reports as
+// stage select_equal, the theta mode's OP_LT / OP_GT as select_compare.
+template <int CMP>
+static uint64_t select_compare(qe_ctx* c, qe_col colA, const uint32_t* a, qe_col colB, const uint32_t* b, uint64_t n,
+                               int nl, const uint32_t* const* in, uint32_t* const* outs) {
     if (n == 0) return 0;
+    const char* stage = CMP == OP_EQ ? "select_equal" : "select_compare";
     const uint32_t* a32 = narrow_of(c, colA.d, colA.n);
     const uint32_t* b32 = narrow_of(c, colB.d, colB.n);
     if (!a32 || !b32) a32 = b32 = nullptr;   // a value of 2^32 or more somewhere: full words
@@ -875,15 +883,15 @@ static uint64_t select_equal(qe_ctx* c, qe_col colA, const uint32_t* a, qe_col c
         if (!a) lists--;
         if (!b && a) lists--;
         const double bytes = (4.0 * lists + (a32 ? 8.0 : 16.0) + (keep ? 0.25 : 0.0)) * (double)n;
-        const SelectEqualOp op{colA.d, colB.d, a32, b32, colA.n, colB.n, a, b, in[0], nl > 1 ? in[1] : nullptr, keep};
-        if (nl > 1) m = run_compact<SE_ITEMS, 2>(c, "select_equal", bytes, op, n, outs[0], outs[1]);
-        else m = run_compact<SE_ITEMS, 1>(c, "select_equal", bytes, op, n, outs[0], nullptr);
+        const SelectCompareOp<CMP> op{colA.d, colB.d, a32, b32, colA.n, colB.n, a, b, in[0], nl > 1 ? in[1] : nullptr, keep};
+        if (nl > 1) m = run_compact<SE_ITEMS, 2>(c, stage, bytes, op, n, outs[0], outs[1]);
+        else m = run_compact<SE_ITEMS, 1>(c, stage, bytes, op, n, outs[0], nullptr);
         for (int k = 2; k < nl; k += 2) {   // the further lists, two per launch, by the kept flags
             const bool two = k + 1 < nl;
             const KeepCarryOp kc{keep, in[k], two ? in[k + 1] : nullptr};
             const double kb = (0.25 + (two ? 8.0 : 4.0)) * (double)n;
-            const uint64_t mk = two ? run_compact<SE_ITEMS, 2>(c, "select_equal", kb, kc, n, outs[k], outs[k + 1])
-                                    : run_compact<SE_ITEMS, 1>(c, "select_equal", kb, kc, n, outs[k], nullptr);
+            const uint64_t mk = two ? run_compact<SE_ITEMS, 2>(c, stage, kb, kc, n, outs[k], outs[k + 1])
+                                    : run_compact<SE_ITEMS, 1>(c, stage, kb, kc, n, outs[k], nullptr);
             if (mk != m) throw Error(QE_EINVAL, "select_equal: carried lists disagree on the survivors");
         }
     } catch (...) {
@@ -894,18 +902,11 @@ static uint64_t select_equal(qe_ctx* c, qe_col colA, const uint32_t* a, qe_col c
     return m;
 }
 
-}  // namespace qe
-
-using namespace qe;
-
-extern "C" {
-
-uint32_t qe_select_equal_tile(void) { return SE_TILE; }
-
-int qe_select_equal(qe_ctx* c, qe_col colA, const qe_list* a, qe_col colB, const qe_list* b, int nl,
-                    const qe_list* const* in, qe_list* outs) {
-    QE_API_BEGIN(c)
+// qe_select_equal (op '=') and qe_select_compare: the checks, the output blocks, the lists' flags
+static void select_api(qe_ctx* c, qe_col colA, const qe_list* a, char op, qe_col colB, const qe_list* b, int nl,
+                       const qe_list* const* in, qe_list* outs) {
     if (nl < 1 || nl > 64 || !in || !in[0] || !outs || !colA.d || !colB.d) throw Error(QE_EINVAL, "select_equal: bad arguments");
+    if (op != '=' && op != '<' && op != '>') throw Error(QE_EINVAL, "select_compare: operator");
     const uint64_t n = in[0]->n;
     for (int k = 0; k < nl; k++)
         if (!in[k] || in[k]->n != n || (n && !in[k]->d)) throw Error(QE_EINVAL, "select_equal: lists of different lengths");
@@ -920,7 +921,11 @@ int qe_select_equal(qe_ctx* c, qe_col colA, const qe_list* a, qe_col colB, const
             outd[made] = dalloc_t<uint32_t>(c, std::max<uint64_t>(n, 1));
             ind[made] = in[made]->d;
         }
-        const uint64_t m = select_equal(c, colA, a ? a->d : nullptr, colB, b ? b->d : nullptr, n, nl, ind, outd);
+        const uint32_t* ad = a ? a->d : nullptr;
+        const uint32_t* bd = b ? b->d : nullptr;
+        const uint64_t m = op == '='   ? select_compare<OP_EQ>(c, colA, ad, colB, bd, n, nl, ind, outd)
+                           : op == '<' ? select_compare<OP_LT>(c, colA, ad, colB, bd, n, nl, ind, outd)
+                                       : select_compare<OP_GT>(c, colA, ad, colB, bd, n, nl, ind, outd);
         for (int k = 0; k < nl; k++) {
             const uint32_t flags = in[k]->flags & QE_LIST_DISTINCT;   // (read before outs[k] is written: it may be in[k])
             outs[k].d = outd[k];
@@ -932,6 +937,28 @@ int qe_select_equal(qe_ctx* c, qe_col colA, const qe_list* a, qe_col colB, const
         for (int k = 0; k < made; k++) dfree(c, outd[k]);
         throw;
     }
+}
+
+}  // namespace qe
+
+using namespace qe;
+
+extern "C" {
+
+uint32_t qe_select_equal_tile(void) { return SE_TILE; }
+
+int qe_select_equal(qe_ctx* c, qe_col colA, const qe_list* a, qe_col colB, const qe_list* b, int nl,
+                    const qe_list* const* in, qe_list* outs) {
+    QE_API_BEGIN(c)
+    select_api(c, colA, a, '=', colB, b, nl, in, outs);
+    return 0;
+    QE_API_END(c)
+}
+
+int qe_select_compare(qe_ctx* c, qe_col colA, const qe_list* a, char op, qe_col colB, const qe_list* b, int nl,
+                      const qe_list* const* in, qe_list* outs) {
+    QE_API_BEGIN(c)
+    select_api(c, colA, a, op, colB, b, nl, in, outs);
     return 0;
     QE_API_END(c)
 }

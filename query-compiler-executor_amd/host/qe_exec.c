@@ -728,6 +728,7 @@ typedef struct {
     atomic_int* stop;          /* the first query index known to end the batch (+1), 0 none */
     int plan;                  /* QE_EXEC_PLAN: the partitioned plan, faithful fallback */
     int relational;            /* QE_EXEC_RELATIONAL: the plan's relational mode, no fallback */
+    int theta;                 /* QE_EXEC_THETA: the relational mode with column </> column honoured */
 } lane_t;
 
 static void* lane_main(void* arg) {
@@ -746,7 +747,8 @@ static void* lane_main(void* arg) {
             L->rcs[i] = QE_ENOMEM;
         } else {
             if (!L->relational) qe_arrange_predicates(&L->qs[i]);
-            L->rcs[i] = L->relational ? qe_plan_exec_query_relational(L->ctx, &L->qs[i], f)
+            L->rcs[i] = L->theta      ? qe_plan_exec_query_theta(L->ctx, &L->qs[i], f)
+                        : L->relational ? qe_plan_exec_query_relational(L->ctx, &L->qs[i], f)
                         : L->plan     ? qe_plan_exec_query(L->ctx, &L->qs[i], f)
                                       : qe_exec_query(L->ctx, &L->qs[i], f);
             fclose(f);
@@ -767,15 +769,19 @@ int qe_run_queries_parallel(qe_ctx* ctx, int workers, const char* text, char** o
 int qe_run_queries_lanes(qe_ctx* ctx, int workers, int executor, const char* text, char** out, size_t* outlen) {
     *out = NULL;
     *outlen = 0;
-    if (executor != QE_EXEC_FAITHFUL && executor != QE_EXEC_PLAN && executor != QE_EXEC_RELATIONAL) return QE_EINVAL;
-    const int relational = executor == QE_EXEC_RELATIONAL;
+    if (executor != QE_EXEC_FAITHFUL && executor != QE_EXEC_PLAN && executor != QE_EXEC_RELATIONAL &&
+        executor != QE_EXEC_THETA)
+        return QE_EINVAL;
+    const int theta = executor == QE_EXEC_THETA;
+    const int relational = executor == QE_EXEC_RELATIONAL || theta;   /* (no arranging, no fallback) */
     const int plan = executor == QE_EXEC_PLAN || relational;   /* (the plan's engine, its shared sorts) */
     if (workers <= 1) {
         if (!plan) return qe_run_queries(ctx, text, out, outlen);
         uint64_t refused = 0;
         int rc = qe_sort_cache(ctx, 1);          /* the batch's base-column sorts, shared */
         if (rc == 0)
-            rc = relational ? qe_run_queries_relational(ctx, NULL, text, out, outlen)
+            rc = theta      ? qe_run_queries_theta(ctx, NULL, text, out, outlen)
+                 : relational ? qe_run_queries_relational(ctx, NULL, text, out, outlen)
                             : qe_run_queries_dist(ctx, NULL, text, out, outlen, &refused);
         const int rc2 = qe_sort_cache(ctx, 0);
         return rc != 0 ? rc : rc2;
@@ -795,7 +801,7 @@ int qe_run_queries_lanes(qe_ctx* ctx, int workers, int executor, const char* tex
     pthread_t th[16];
     int started = 0;
     for (int k = 0; k < workers; k++) {
-        lane_t l = {w[k], qs, nq, &next, outs, lens, rcs, &stop, plan, relational};
+        lane_t l = {w[k], qs, nq, &next, outs, lens, rcs, &stop, plan, relational, theta};
         lanes[k] = l;
         if (pthread_create(&th[k], NULL, lane_main, &lanes[k]) == 0) started++;
         else break;

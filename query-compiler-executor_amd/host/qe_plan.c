@@ -1153,19 +1153,60 @@ static int plan_query(const qe_engine* e, const query_t* q, FILE* out, uint64_t*
 
 /* QE_EINVAL / QE_ENOTSUP with the reason, or 0: every rank decides on the text and the relations'
  * shapes alone, so all of them leave a bad query together before any collective */
-static int rel_validate(const qe_engine* e, const query_t* q) {
+/* the representative of every binding under the query's column = column predicates (malloc'd) */
+static int* rel_eq_roots(const query_t* q) {
+    int* parent = (int*)malloc((q->nrels + 1) * sizeof(int));
+    for (size_t i = 0; i <= q->nrels; i++) parent[i] = (int)i;
+    for (size_t i = 0; i < q->npreds; i++) {
+        const pred_t* p = &q->preds[i];
+        if (p->type == 0 && p->op == '=') parent[uf_find(parent, (int)p->frel)] = uf_find(parent, (int)p->srel);
+    }
+    for (size_t i = 0; i <= q->nrels; i++) parent[i] = uf_find(parent, (int)i);
+    return parent;
+}
+
+/* theta mode: a column < / > column predicate between two bindings that no chain of = predicates
+ * connects links their two components; a component takes part in at most one link */
+static int theta_validate(const query_t* q) {
+    int* root = rel_eq_roots(q);
+    int* links = (int*)calloc(q->nrels + 1, sizeof(int));
+    int* other = (int*)malloc((q->nrels + 1) * sizeof(int));
+    int rc = 0;
+    for (size_t i = 0; rc == 0 && i < q->npreds; i++) {
+        const pred_t* p = &q->preds[i];
+        if (p->type != 0 || p->op == '=') continue;
+        const int a = root[p->frel], b = root[p->srel];
+        if (a == b) continue;                                /* a filter or an in-component selection */
+        if (links[a] && links[b] && other[a] == b)
+            rc = refuse("two column </> column predicates between the same two unconnected components (a band)");
+        else if (links[a] || links[b])
+            rc = refuse("a component with two or more column </> column links (a chain or a tree of links)");
+        links[a]++;
+        links[b]++;
+        other[a] = b;
+        other[b] = a;
+    }
+    free(root);
+    free(links);
+    free(other);
+    return rc;
+}
+
+static int rel_validate(const qe_engine* e, const query_t* q, int theta) {
     g_why[0] = 0;
     if (!e->select_eq) return refuse("the engine has no select_eq"), QE_EINVAL;
+    if (theta && !(e->select_cmp && e->allgather && e->theta_weights && e->checksums_weighted))
+        return refuse("the engine lacks a theta callback"), QE_EINVAL;
     if (!s_query_valid(e, q)) return refuse("out-of-range relation / column / binding"), QE_EINVAL;
     if (q->nsel == 0) return refuse("no select"), QE_EINVAL;
     if (q->nrels > 60) return refuse("more than 60 bindings"), QE_EINVAL;   /* (side_t's carried bindings) */
     for (size_t i = 0; i < q->npreds; i++) {
         const pred_t* p = &q->preds[i];
         if (!op_valid(p->op)) return refuse("operator '%c'", p->op), QE_EINVAL;
-        if (p->type == 0 && p->op != '=')   /* (the reference joins on equality whatever is written) */
+        if (p->type == 0 && p->op != '=' && !theta)   /* (the reference joins on equality whatever is written) */
             return refuse("column %c column is not an equi-join", p->op);
     }
-    return 0;
+    return theta ? theta_validate(q) : 0;
 }
 
 /* does some column = column predicate of q run inside a component, whatever the join order?  A
@@ -1232,12 +1273,17 @@ static int rel_filter_binding(plan_t* P, int b, int hints) {
     ECHK(frc);
     for (size_t i = 0; i < q->npreds; i++) {                 /* b.x = b.y: a filter on b's rows */
         const pred_t* p = &q->preds[i];
-        if (p->type != 0 || (int)p->frel != b || (int)p->srel != b || p->fcol == p->scol) continue;
+        if (p->type != 0 || (int)p->frel != b || (int)p->srel != b) continue;
+        if (p->fcol == p->scol && p->op == '=') continue;    /* (theta mode: b.x < b.x keeps nothing) */
         touched = 1;
         ECHK(rel_list_of(P, b));
         qe_h nl = NONE;
-        ECHK(e->select_eq(e->u, relid, (uint32_t)p->fcol, P->list[b], relid, (uint32_t)p->scol, P->list[b], 1,
-                          &P->list[b], &nl));
+        if (p->op == '=')
+            ECHK(e->select_eq(e->u, relid, (uint32_t)p->fcol, P->list[b], relid, (uint32_t)p->scol, P->list[b], 1,
+                              &P->list[b], &nl));
+        else
+            ECHK(e->select_cmp(e->u, relid, (uint32_t)p->fcol, P->list[b], p->op, relid, (uint32_t)p->scol,
+                               P->list[b], 1, &P->list[b], &nl));
         rel(P, P->list[b]);
         P->list[b] = nl;
     }
@@ -1270,8 +1316,12 @@ static int rel_select_in_comp(plan_t* P, const pred_t* p) {
         in[i] = c->m[i].rows;
         outs[i] = NONE;
     }
-    ECHK(e->select_eq(e->u, P->q->rels[p->frel], (uint32_t)p->fcol, c->m[ia].rows, P->q->rels[p->srel],
-                      (uint32_t)p->scol, c->m[ib].rows, c->n, in, outs));
+    if (p->op == '=')
+        ECHK(e->select_eq(e->u, P->q->rels[p->frel], (uint32_t)p->fcol, c->m[ia].rows, P->q->rels[p->srel],
+                          (uint32_t)p->scol, c->m[ib].rows, c->n, in, outs));
+    else                                                     /* (theta mode: the written operator) */
+        ECHK(e->select_cmp(e->u, P->q->rels[p->frel], (uint32_t)p->fcol, c->m[ia].rows, p->op, P->q->rels[p->srel],
+                           (uint32_t)p->scol, c->m[ib].rows, c->n, in, outs));
     for (int i = 0; i < c->n; i++) {
         rel(P, c->m[i].rows);
         c->m[i].rows = outs[i];
@@ -1283,8 +1333,51 @@ static int rel_select_in_comp(plan_t* P, const pred_t* p) {
     return 0;
 }
 
-static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint64_t* rows_out) {
-    int rc = rel_validate(e, q);
+/* a theta link (theta mode): components A and B under kA op kB; wA / wB the per-row partner counts
+ * of this rank's rows of A / B (uint32 lists aligned with the components' member lists), P the
+ * pair count (this rank's share until the all-reduce) */
+typedef struct { int A, B; qe_h wA, wB; uint64_t P; } link_t;
+
+static char flip_op(char op) { return op == '<' ? '>' : op == '>' ? '<' : op; }
+
+/* one link: both sides' keys (all-gathered at N ranks: every rank holds both sides, 8 B per row),
+ * the weights of this rank's rows of each side against the whole other side.  A's weights always
+ * (their sum is the pair share); B's, and the gather of A's keys they need, only when a select
+ * reads a binding of B -- decided on the text, so every rank makes the same collectives */
+static int rel_link(plan_t* P, const pred_t* p, link_t* L) {
+    const qe_engine* e = P->e;
+    L->A = P->comp_of[p->frel];
+    L->B = P->comp_of[p->srel];
+    if (P->C[L->A].size >> 32 || P->C[L->B].size >> 32) {    /* global sizes: every rank leaves here */
+        P->rc = QE_ETOOBIG;
+        return refuse("a column %c column link side of 2^32 rows or more", p->op), QE_ETOOBIG;
+    }
+    qe_h k[2] = {NONE, NONE}, all[2] = {NONE, NONE};
+    int rc = 0, need_b = 0;
+    for (size_t s = 0; s < P->q->nsel; s++) need_b |= P->comp_of[P->q->sel[2 * s]] == L->B;
+    for (int t = 0; rc == 0 && t < 2; t++) {
+        comp_t* c = &P->C[t ? L->B : L->A];
+        const int b = (int)(t ? p->srel : p->frel);
+        member* m = &c->m[member_idx(c, b)];
+        if (m->vcol) rc = QE_EINVAL;                         /* (a reader of rowids that the hints missed) */
+        if (rc == 0) rc = rows_of(P, m);
+        if (rc == 0) rc = e->keys(e->u, P->q->rels[b], (uint32_t)(t ? p->scol : p->fcol), m->rows, &k[t]);
+        if (rc == 0 && e->world > 1 && (t == 1 || need_b)) rc = e->allgather(e->u, k[t], &all[t]);
+    }
+    uint64_t pb = 0;
+    if (rc == 0) rc = e->theta_weights(e->u, k[0], e->world > 1 ? all[1] : k[1], p->op, &L->wA, &L->P);
+    if (rc == 0 && need_b)
+        rc = e->theta_weights(e->u, k[1], e->world > 1 ? all[0] : k[0], flip_op(p->op), &L->wB, &pb);
+    for (int t = 0; t < 2; t++) {
+        rel(P, k[t]);
+        rel(P, all[t]);
+    }
+    if (rc) P->rc = rc;
+    return rc;
+}
+
+static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint64_t* rows_out, int theta) {
+    int rc = rel_validate(e, q, theta);
     if (rc) return rc;
     plan_t PP;
     plan_t* P = &PP;
@@ -1305,10 +1398,15 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
     int* kcol1 = (int*)calloc(nb, sizeof(int));
     int* vok = (int*)calloc(nb, sizeof(int));
     int* pending = (int*)malloc((q->npreds + 1) * sizeof(int));
+    /* theta mode: a column < / > column predicate between two bindings reads their rowids after the
+     * joins (a selection, or a link's keys), so nothing of such a query rides as values */
+    int cross = 0;
+    for (size_t i = 0; i < q->npreds; i++)
+        cross |= q->preds[i].type == 0 && q->preds[i].op != '=' && q->preds[i].frel != q->preds[i].srel;
     /* a query with a selection inside a component: its bindings' rowids are read by a predicate
      * that is no join, so no binding rides as its next join's key or as a column's values on the
      * strength of "its only remaining predicate is a join" (kcol1 / vok / the scans' hints off) */
-    const int selection = rel_has_selection(q);
+    const int selection = rel_has_selection(q) || cross;
     int zero = 0;                                            /* some component is empty: every select is NULL */
     for (size_t b = 0; rc == 0 && b < q->nrels; b++) {
         rc = rel_filter_binding(P, (int)b, !selection);
@@ -1327,15 +1425,16 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
             }
         }
         const int inside = jbest < np;
-        if (!inside) {
-            jbest = 0;
-            if (P->reorder) {                                /* greedy: the smallest |A| + |B| first */
-                uint64_t best = UINT64_MAX;
-                for (size_t i = 0; i < np; i++) {
-                    const uint64_t c = join_cost(P, &q->preds[pending[i]]);
-                    if (c < best) { best = c; jbest = i; }
-                }
+        if (!inside) {                                       /* the next equi-join (a < / > predicate never joins) */
+            uint64_t best = UINT64_MAX;
+            for (size_t i = 0; i < np; i++) {
+                if (q->preds[pending[i]].op != '=') continue;
+                if (jbest == np) jbest = i;
+                if (!P->reorder) break;
+                const uint64_t c = join_cost(P, &q->preds[pending[i]]);   /* greedy: the smallest |A| + |B| first */
+                if (c < best) { best = c; jbest = i; }
             }
+            if (jbest == np) break;                          /* theta links remain: after every join, below */
         }
         const pred_t* jp = &q->preds[pending[jbest]];
         for (size_t i = jbest; i + 1 < np; i++) pending[i] = pending[i + 1];
@@ -1350,61 +1449,92 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
             memset(kcol1, 0, nb * sizeof(int));
             memset(vok, 0, nb * sizeof(int));
         }
+        if (cross) memset(sel1, 0, nb * sizeof(int));
         rc = do_join(P, jp, need, sel1, kcol1, vok, np == 0);
         if (rc == 0 && (P->agg ? P->agg_size : P->C[P->comp_of[jp->frel]].size) == 0) zero = 1;
     }
     /* every binding belongs to a component: one no predicate joined is its list, or its whole relation */
     for (size_t b = 0; rc == 0 && !zero && b < q->nrels; b++)
         if (P->comp_of[b] < 0) (void)component(P, (int)b);
-    /* total = the product of the component sizes (the aggregate last join's pair count is one);
-     * a select prints its component's sum times the other components' sizes, mod 2^64 */
-    uint64_t* sums = (uint64_t*)calloc(q->nsel + 1, sizeof(uint64_t));
+    /* theta mode: what is still pending links two components (rel_validate: at most one link each) */
+    link_t* links = (link_t*)calloc(np + 1, sizeof(link_t));
+    int* link_of = (int*)malloc((2 * nb + q->npreds + 1) * sizeof(int));
+    for (size_t i = 0; i < 2 * nb + q->npreds + 1; i++) link_of[i] = -1;
+    int nl = 0;
+    for (size_t i = 0; rc == 0 && !zero && i < np; i++) {
+        rc = rel_link(P, &q->preds[pending[i]], &links[nl]);
+        link_of[links[nl].A] = link_of[links[nl].B] = nl;
+        nl++;
+    }
+    /* the selects' sums: a select prints its component's sum times the other components' sizes, mod
+     * 2^64; a linked component's rows count with their weights, and the pair is one component of P */
+    uint64_t* sums = (uint64_t*)calloc(q->nsel + (size_t)nl + 1, sizeof(uint64_t));
     uint64_t* mult = (uint64_t*)calloc(q->nsel + 1, sizeof(uint64_t));
     uint32_t* srel = (uint32_t*)calloc(q->nsel + 1, sizeof(uint32_t));
     uint32_t* scol = (uint32_t*)calloc(q->nsel + 1, sizeof(uint32_t));
     qe_h* srows = (qe_h*)calloc(q->nsel + 1, sizeof(qe_h));
+    qe_h* sw = (qe_h*)calloc(q->nsel + 1, sizeof(qe_h));
     int* at = (int*)calloc(q->nsel + 1, sizeof(int));
+    int* scomp = (int*)calloc(q->nsel + 1, sizeof(int));
+    for (int w = 0; w < 2; w++) {                            /* plain checksums, then the weighted ones */
+        int ns = 0;
+        for (size_t s = 0; rc == 0 && !zero && s < q->nsel; s++) {
+            const int b = (int)q->sel[2 * s];
+            const int ci = P->C[P->comp_of[b]].alive ? P->comp_of[b] : -1;   /* -1: the aggregate last join's */
+            scomp[s] = ci;
+            if (ci < 0) {
+                sums[s] = P->agg_sums[s];
+                continue;
+            }
+            if ((link_of[ci] >= 0) != w) continue;
+            comp_t* c = &P->C[ci];
+            member* mb = &c->m[member_idx(c, b)];
+            rc = rows_of(P, mb);
+            if (w && mb->vcol) rc = P->rc = QE_EINVAL;        /* (a linked query carries rowids only) */
+            srel[ns] = mb->vcol ? QE_PLAN_VALUES : q->rels[b];
+            scol[ns] = (uint32_t)q->sel[2 * s + 1];
+            srows[ns] = mb->rows;
+            if (w) sw[ns] = links[link_of[ci]].A == ci ? links[link_of[ci]].wA : links[link_of[ci]].wB;
+            at[ns++] = (int)s;
+        }
+        if (rc == 0 && ns) {
+            uint64_t* part = (uint64_t*)calloc((size_t)ns, sizeof(uint64_t));
+            rc = w ? e->checksums_weighted(e->u, ns, srel, scol, srows, sw, part)
+                   : e->checksums(e->u, ns, srel, scol, srows, part);
+            for (int k = 0; k < ns; k++) sums[at[k]] = part[k];
+            free(part);
+        }
+    }
+    /* one all-reduce: the sums and, behind them, every link's pair share */
+    for (int l = 0; l < nl; l++) sums[q->nsel + (size_t)l] = links[l].P;
+    if (rc == 0 && !zero && e->world > 1) rc = e->allreduce(e->u, sums, (int)q->nsel + nl);
+    for (int l = 0; l < nl; l++) links[l].P = sums[q->nsel + (size_t)l];
+    /* total = the product of the component sizes (the aggregate last join's pair count is one, and so
+     * is a linked pair's P) */
     uint64_t total = 1;
     if (rc == 0 && !zero) {
         int sat = 0;
         for (int i = -1; i < P->nc; i++) {
             if (i < 0 ? !P->agg : !P->C[i].alive) continue;
-            const uint64_t sz = i < 0 ? P->agg_size : P->C[i].size;
+            if (i >= 0 && link_of[i] >= 0 && links[link_of[i]].B == i) continue;   /* (counted with its A) */
+            const uint64_t sz = i < 0 ? P->agg_size : link_of[i] >= 0 ? links[link_of[i]].P : P->C[i].size;
             if (sz == 0) zero = 1;
             if (__builtin_mul_overflow(total, sz, &total)) sat = 1;
         }
         if (sat) total = UINT64_MAX;
     }
     if (zero) total = 0;
-    int ns = 0;
     for (size_t s = 0; rc == 0 && !zero && s < q->nsel; s++) {
-        const int b = (int)q->sel[2 * s];
-        const int ci = P->C[P->comp_of[b]].alive ? P->comp_of[b] : -1;   /* -1: the aggregate last join's */
+        const int ci = scomp[s];
+        const int li = ci >= 0 ? link_of[ci] : -1;
         uint64_t m = 1;
         for (int i = -1; i < P->nc; i++) {
             if (i == ci || (i < 0 ? !P->agg : !P->C[i].alive)) continue;
-            m *= i < 0 ? P->agg_size : P->C[i].size;
+            if (i >= 0 && link_of[i] >= 0 && (link_of[i] == li || links[link_of[i]].B == i)) continue;
+            m *= i < 0 ? P->agg_size : link_of[i] >= 0 ? links[link_of[i]].P : P->C[i].size;
         }
         mult[s] = m;
-        if (ci < 0) {
-            sums[s] = P->agg_sums[s];
-            continue;
-        }
-        comp_t* c = &P->C[ci];
-        member* mb = &c->m[member_idx(c, b)];
-        rc = rows_of(P, mb);
-        srel[ns] = mb->vcol ? QE_PLAN_VALUES : q->rels[b];
-        scol[ns] = (uint32_t)q->sel[2 * s + 1];
-        srows[ns] = mb->rows;
-        at[ns++] = (int)s;
     }
-    if (rc == 0 && ns) {
-        uint64_t* part = (uint64_t*)calloc((size_t)ns, sizeof(uint64_t));
-        rc = e->checksums(e->u, ns, srel, scol, srows, part);
-        for (int k = 0; k < ns; k++) sums[at[k]] = part[k];
-        free(part);
-    }
-    if (rc == 0 && !zero && e->world > 1) rc = e->allreduce(e->u, sums, (int)q->nsel);
     if (rc == 0) {
         for (size_t s = 0; s < q->nsel; s++) {
             if (zero) fputs("NULL ", out);
@@ -1413,12 +1543,20 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
         fputc('\n', out);
         if (rows_out) *rows_out = total;
     }
+    for (int l = 0; l < nl; l++) {
+        rel(P, links[l].wA);
+        rel(P, links[l].wB);
+    }
+    free(links);
+    free(link_of);
     free(sums);
     free(mult);
     free(srel);
     free(scol);
     free(srows);
+    free(sw);
     free(at);
+    free(scomp);
     for (int i = 0; i < P->nc; i++)
         if (P->C[i].alive) free_comp(P, i);
     for (size_t b = 0; b < nb; b++) rel(P, P->list[b]);
@@ -1507,7 +1645,7 @@ int qe_plan_run_text(const qe_engine* e, const char* text, char** out, size_t* o
     return rc;
 }
 
-int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uint64_t* rows) {
+static int run_query_rel(const qe_engine* e, void* query, void* out, uint64_t* rows, int theta) {
     /* the query's bytes are buffered: a query that fails prints nothing (the batch's output ends with
      * the query before it) */
     char* qbuf = NULL;
@@ -1515,7 +1653,7 @@ int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uin
     FILE* qf = open_memstream(&qbuf, &qlen);
     if (!qf) return QE_ENOMEM;
     uint64_t r = 0;
-    const int rc = plan_query_rel(e, (const query_t*)query, qf, &r);
+    const int rc = plan_query_rel(e, (const query_t*)query, qf, &r, theta);
     fclose(qf);
     if (rc == 0) {
         if (qlen) fwrite(qbuf, 1, qlen, (FILE*)out);
@@ -1525,7 +1663,7 @@ int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uin
     return rc;
 }
 
-int qe_plan_run_text_relational(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows) {
+static int run_text_rel(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows, int theta) {
     *out = NULL;
     *outlen = 0;
     FILE* f = open_memstream(out, outlen);
@@ -1533,8 +1671,24 @@ int qe_plan_run_text_relational(const qe_engine* e, const char* text, char** out
     size_t nq = 0;
     query_t* qs = qe_parse_text(text, &nq);     /* parsed before anything runs (main/queries_main.c:31-37) */
     int rc = 0;
-    for (size_t i = 0; rc == 0 && i < nq; i++) rc = qe_plan_run_query_relational(e, &qs[i], f, rows);
+    for (size_t i = 0; rc == 0 && i < nq; i++) rc = run_query_rel(e, &qs[i], f, rows, theta);
     qe_free_queries(qs, nq);
     fclose(f);
     return rc;
+}
+
+int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uint64_t* rows) {
+    return run_query_rel(e, query, out, rows, 0);
+}
+
+int qe_plan_run_text_relational(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows) {
+    return run_text_rel(e, text, out, outlen, rows, 0);
+}
+
+int qe_plan_run_query_theta(const qe_engine* e, void* query, void* out, uint64_t* rows) {
+    return run_query_rel(e, query, out, rows, 1);
+}
+
+int qe_plan_run_text_theta(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows) {
+    return run_text_rel(e, text, out, outlen, rows, 1);
 }

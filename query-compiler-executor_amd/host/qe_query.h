@@ -73,6 +73,9 @@ int qe_plan_exec_query(struct qe_ctx* ctx, query_t* q, FILE* out);
 /* csrc/qe_comm.hip: one parsed query through the plan's relational mode on this ctx alone (one
  * rank): the textbook answer, or an error and no output (include/qe_plan.h) */
 int qe_plan_exec_query_relational(struct qe_ctx* ctx, query_t* q, FILE* out);
+/* csrc/qe_comm.hip: the same through the plan's theta mode (a written column < / > column predicate
+ * honoured) */
+int qe_plan_exec_query_theta(struct qe_ctx* ctx, query_t* q, FILE* out);
 
 #ifdef __cplusplus
 }

@@ -16,9 +16,10 @@ LIB_PATH = os.environ.get("QE_LIB_PATH") or os.path.join(PKG, "build", "libqe.so
 HEADER = os.path.join(os.path.dirname(PKG), "include", "qe.h")
 
 QE_EINVAL, QE_EHIP, QE_ENOMEM, QE_EEXIT, QE_ETOOBIG, QE_ENOTSUP = -1, -2, -3, -4, -5, -6
-QE_EXEC_FAITHFUL, QE_EXEC_PLAN, QE_EXEC_RELATIONAL = 0, 1, 2   # qe_run_queries_lanes' executors
+QE_EXEC_FAITHFUL, QE_EXEC_PLAN, QE_EXEC_RELATIONAL, QE_EXEC_THETA = 0, 1, 2, 3   # qe_run_queries_lanes' executors
 LIST_DISTINCT = 1
 PAIRS_DISTINCT, PAIRS_SORTED = 1, 2
+PAIRS_MATCHED = 8
 
 
 class Col(C.Structure):
@@ -149,6 +150,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "qe_run_queries_relational": (I, [P, P, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
         "qe_run_queries_relational_local": (I, [P, I, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                 C.POINTER(C.c_uint64)]),
+        "qe_select_compare": (I, [P, Col, C.POINTER(List), C.c_char, Col, C.POINTER(List), I,
+                                  C.POINTER(C.POINTER(List)), C.POINTER(List)]),
+        "qe_theta_counts": (I, [P, C.POINTER(Pairs), C.POINTER(Pairs), C.c_char, C.POINTER(C.c_uint64)]),
+        "qe_allgather_u64": (I, [P, P, P, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+        "qe_run_queries_theta": (I, [P, P, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+        "qe_run_queries_theta_local": (I, [P, I, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_uint64)]),
         "qe_bind_thread": (I, [P]),
     }
     for name, (res, args) in sig.items():
@@ -266,7 +274,7 @@ class Ctx:
         s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
         if out.value:
             self.lib.qe_free_host(out)
-        if executor == QE_EXEC_RELATIONAL:
+        if executor in (QE_EXEC_RELATIONAL, QE_EXEC_THETA):
             return s, self._relational_code(rc)
         if rc not in (0, QE_EEXIT):
             raise QEError(rc, self.lib.qe_last_error(self.h).decode())
@@ -297,6 +305,28 @@ class Ctx:
         out, n, sent = C.c_void_p(), C.c_size_t(), C.c_uint64()
         rc = self.lib.qe_run_queries_relational_local(self.h, nranks, text.encode(), C.byref(out), C.byref(n),
                                                       C.byref(sent))
+        s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
+        if out.value:
+            self.lib.qe_free_host(out)
+        return s, self._relational_code(rc), sent.value
+
+    def run_theta(self, text: str, comm: "Comm | None" = None) -> tuple[str, int]:
+        """qe_run_queries_theta: run_relational with a written column < / > column predicate
+        honoured (a filter, a selection inside a component or a link of two components) ->
+        (stdout on rank 0, 0 or the code that ended the batch)"""
+        out, n = C.c_void_p(), C.c_size_t()
+        rc = self.lib.qe_run_queries_theta(self.h, comm.h if comm else None, text.encode(), C.byref(out), C.byref(n))
+        s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
+        if out.value:
+            self.lib.qe_free_host(out)
+        return s, self._relational_code(rc)
+
+    def run_theta_local(self, text: str, nranks: int) -> tuple[str, int, int]:
+        """qe_run_queries_theta_local: the same on `nranks` in-process ranks of this GPU ->
+        (stdout, 0 or the code that ended the batch, bytes exchanged)"""
+        out, n, sent = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        rc = self.lib.qe_run_queries_theta_local(self.h, nranks, text.encode(), C.byref(out), C.byref(n),
+                                                 C.byref(sent))
         s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
         if out.value:
             self.lib.qe_free_host(out)
@@ -400,6 +430,22 @@ class Ctx:
         self._chk(self.lib.qe_select_equal(self.h, colA, C.byref(a) if a is not None else None, colB,
                                            C.byref(b) if b is not None else None, n, inp, outs))
         return [outs[i] for i in range(n)]
+
+    def select_compare(self, colA: Col, a: List | None, op: str, colB: Col, b: List | None,
+                       lists: list[List]) -> list[List]:
+        """qe_select_compare: select_equal with the written operator, one of '=', '<', '>'"""
+        n = len(lists)
+        inp = (C.POINTER(List) * n)(*[C.pointer(l) for l in lists])
+        outs = (List * n)()
+        self._chk(self.lib.qe_select_compare(self.h, colA, C.byref(a) if a is not None else None, op.encode(), colB,
+                                             C.byref(b) if b is not None else None, n, inp, outs))
+        return [outs[i] for i in range(n)]
+
+    def theta_counts(self, R: Pairs, S: Pairs, op: str) -> int:
+        """qe_theta_counts: R.match[i] = #{j : R.key[i] op S.key[j]} for two sorted sides -> their sum"""
+        pairs = C.c_uint64()
+        self._chk(self.lib.qe_theta_counts(self.h, C.byref(R), C.byref(S), op.encode(), C.byref(pairs)))
+        return pairs.value
 
     def select_equal_tile(self) -> int:
         return int(self.lib.qe_select_equal_tile())
@@ -629,6 +675,25 @@ class Comm:
         self.ctx._chk(self.lib.qe_allreduce_u64(self.ctx.h, self.h, a, len(vals)))
         return list(a)
 
+    def allgather(self, keys: np.ndarray) -> np.ndarray:
+        """qe_allgather_u64 of a host array through the device: every rank's keys, in rank order
+        (every rank of the communicator calls it; the counts may differ and may be 0)"""
+        ctx = self.ctx
+        p = ctx.pairs_from_host(keys, np.zeros(len(keys), dtype=np.uint32))
+        out, n = C.c_void_p(), C.c_uint64()
+        try:
+            ctx._chk(self.lib.qe_allgather_u64(ctx.h, self.h, p.key, p.n, C.byref(out), C.byref(n)))
+        finally:
+            ctx.pairs_free(p)
+        view = Pairs()
+        view.key, view.n = out.value, n.value
+        got = np.empty(n.value, dtype=np.uint64)
+        try:
+            ctx._chk(self.lib.qe_pairs_to_host(ctx.h, C.byref(view), got.ctypes.data, None))
+        finally:
+            ctx.buffer_free(out)
+        return got
+
     def shuffle(self, keys_ptr: int, n: int, col_ptrs: list[int]):
         """qe_shuffle_pairs -> (keys ptr, [col ptrs], n) in ctx buffers (free with ctx.buffer_free)"""
         cols = (C.c_void_p * max(1, len(col_ptrs)))(*col_ptrs)
@@ -672,6 +737,25 @@ class LocalComms:
             try:
                 self.lib.qe_bind_thread(self.ctxs[r].h)
                 res[r] = self.ctxs[r].run_dist(text, self.comms[r])
+            except QEError as e:
+                res[r] = e
+        th = [threading.Thread(target=go, args=(r,)) for r in range(len(self.ctxs))]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+        return res
+
+    def allgather(self, keys: list[np.ndarray]) -> list:
+        """Comm.allgather on every rank from its own host thread, keys[r] being rank r's array ->
+        per rank: the concatenation, or the QEError it raised"""
+        import threading
+        res = [None] * len(self.ctxs)
+
+        def go(r):
+            try:
+                self.lib.qe_bind_thread(self.ctxs[r].h)
+                res[r] = self.comms[r].allgather(keys[r])
             except QEError as e:
                 res[r] = e
         th = [threading.Thread(target=go, args=(r,)) for r in range(len(self.ctxs))]
