@@ -143,6 +143,9 @@ int  qe_run_queries_parallel(qe_ctx*, int workers, const char* text, char** out,
 /* QE_EXEC_THETA: the same through the plan's theta mode (qe_run_queries_theta below): a written
  * column < / > column predicate is honoured instead of refused */
 #define QE_EXEC_THETA 3
+/* QE_EXEC_THETA_TREE: the same through the plan's theta-tree mode (qe_run_queries_theta_tree below):
+ * any forest of column < / > column links between components, not one link per component */
+#define QE_EXEC_THETA_TREE 4
 int  qe_run_queries_lanes(qe_ctx*, int workers, int executor, const char* text, char** out, size_t* outlen);
 /* A batch's shared sorts of whole base columns (no reference counterpart: the reference sorts a
  * base relation again for every join, src/join.c:122-142 + :5-94).  on = 1: from now on the first
@@ -249,6 +252,24 @@ int qe_checksum_weighted(qe_ctx*, qe_col col, const qe_pairs* p, uint64_t* sum);
  * tiles of 4096 keys: two searches bound the tile's window of S, each key finds its bound inside
  * the window -- staged in LDS when it fits, read from global memory when it does not. */
 int qe_theta_counts(qe_ctx*, qe_pairs* R, const qe_pairs* S, char op, uint64_t* pairs);
+/* Theta-tree mode's link (no reference counterpart): qe_theta_counts with a
+ * weight per row of S.  out[R.val[i]] = (mul ? mul[R.val[i]] : 1) * sum_{j : R.key[i] op S.key[j]}
+ * sw[S.val[j]] mod 2^64, *total = the sum of out mod 2^64.  sw: device weights indexed by S's original
+ * positions (S.val; a null val is position j), S.n of them, NULL for all ones -- the sums are then
+ * qe_theta_counts' counts.  mul (optional) and out: device words indexed by R's original positions,
+ * R.n of each; R.val and S.val hold positions below R.n / S.n (one outside is skipped / weighs 0).
+ * The same preconditions and codes as qe_theta_counts; R is not changed.  The weights are gathered
+ * into S's sorted order inside an exclusive scan (never stored permuted), then one pass over R in
+ * qe_theta_counts' tiles looks each key's bound up in the prefix sums. */
+int qe_theta_wsums(qe_ctx*, const qe_pairs* R, const qe_pairs* S, const uint64_t* sw, char op, const uint64_t* mul,
+                   uint64_t* out, uint64_t* total);
+/* A device array of n uint64 words (at least one allocated) copied from the host, and back;
+ * release with qe_buffer_free.  qe_theta_wsums' weights, multipliers and sums. */
+int qe_u64_from_host(qe_ctx*, const uint64_t* h, uint64_t n, uint64_t** d);
+int qe_u64_to_host(qe_ctx*, const uint64_t* d, uint64_t n, uint64_t* h);
+/* *sum = sum_i col[rows[i]] * w[i] mod 2^64 with 64-bit device weights w (rows->n of them; rows ==
+ * NULL: every row of the column in order) -- qe_checksum_weighted for qe_theta_wsums' output. */
+int qe_checksum_weighted64(qe_ctx*, qe_col col, const qe_list* rows, const uint64_t* w, uint64_t* sum);
 /* a8 + print_sums, aggregate form for two BASE columns (C5: the query's last join, each side's
  * selects on at most one column): with c_i = #S rows whose key equals R.key[i] (and symmetric),
  * out[0] = sum_i c_i = the join's pair count P, out[1] = sum_i valR[i] * c_i and out[2] =
@@ -339,6 +360,13 @@ int  qe_run_queries_relational(qe_ctx*, qe_comm*, const char* text, char** out, 
  * or a link between two components; a query without one prints the relational mode's line.
  * QE_ENOTSUP: a component with two or more links; QE_ETOOBIG: a link side of 2^32 rows or more. */
 int  qe_run_queries_theta(qe_ctx*, qe_comm*, const char* text, char** out, size_t* outlen);
+/* Theta-tree mode (include/qe_plan.h qe_plan_run_text_theta_tree): theta mode
+ * with chains and trees of links -- the link graph over the components may be any forest; each tree
+ * counts as one component of as many rows as row tuples satisfy all its links.  A query whose
+ * components have at most one link each prints theta mode's line.  QE_ENOTSUP: a cycle of links, or
+ * two links between the same two components (a band); QE_ETOOBIG: a link side of 2^32 rows or more,
+ * or a tree whose components' sizes multiply to 2^64 or more. */
+int  qe_run_queries_theta_tree(qe_ctx*, qe_comm*, const char* text, char** out, size_t* outlen);
 /* Concatenate every rank's device array d[0..n) in rank order into *out (a new device buffer of
  * *out_n words, at least one allocated; release with qe_buffer_free).  The counts differ per rank
  * and may be 0.  comm == NULL or one rank: a copy.  Every rank of the communicator calls it. */
@@ -364,6 +392,9 @@ int  qe_run_queries_relational_local(qe_ctx*, int nranks, const char* text, char
 /* qe_run_queries_theta on nranks (1..16) in-process ranks, as qe_run_queries_local */
 int  qe_run_queries_theta_local(qe_ctx*, int nranks, const char* text, char** out, size_t* outlen,
                                 uint64_t* bytes_sent);
+/* qe_run_queries_theta_tree on nranks (1..16) in-process ranks, as qe_run_queries_local */
+int  qe_run_queries_theta_tree_local(qe_ctx*, int nranks, const char* text, char** out, size_t* outlen,
+                                     uint64_t* bytes_sent);
 
 /* The ctx's HIP stream (hipStream_t), for callers that order their own work against it. */
 int qe_sync_stream_ptr(qe_ctx*, void** stream);

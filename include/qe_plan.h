@@ -157,6 +157,16 @@ typedef struct qe_engine {
      * (everything borrowed; rels[k] is never QE_PLAN_VALUES) */
     int (*checksums_weighted)(void* u, int n, const uint32_t* rels, const uint32_t* cols, const qe_h* rows,
                               const qe_h* w, uint64_t* sums);
+    /* THETA-TREE MODE ONLY (the _theta_tree entry points below; no other entry point reads these two,
+     * and the theta-tree entry points return QE_EINVAL when one of them or a theta callback is missing).
+     * *out (uint64, aligned with qk): out[i] = (mul ? mul[i] : 1) * sum_{j : qk[i] op sk[j]} sw[j] mod
+     * 2^64, op '<' or '>'; *total = the sum of out mod 2^64.  qk, sk (uint64 keys), sw (uint64 weights
+     * aligned with sk, in any common order; 0: all ones) and mul (uint64 aligned with qk; 0: none) are
+     * borrowed.  QE_ETOOBIG: a side of 2^32 keys or more. */
+    int (*theta_wsums)(void* u, qe_h qk, qe_h sk, qe_h sw, char op, qe_h mul, qe_h* out, uint64_t* total);
+    /* checksums_weighted with uint64 weights (theta_wsums' lists) */
+    int (*checksums_weighted64)(void* u, int n, const uint32_t* rels, const uint32_t* cols, const qe_h* rows,
+                                const qe_h* w, uint64_t* sums);
 } qe_engine;
 
 /* Replay the reference's variant choice and list bookkeeping for every query of `text` on the
@@ -210,6 +220,26 @@ int qe_plan_run_query_relational(const qe_engine* e, void* query, void* out, uin
  * ranks (the per-row counts are uint32).  QE_EINVAL: an engine without the four theta callbacks. */
 int qe_plan_run_text_theta(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows);
 int qe_plan_run_query_theta(const qe_engine* e, void* query, void* out, uint64_t* rows);
+
+/* Theta-tree mode: theta mode with the link rule widened.  The link graph has the
+ * components as nodes and the < / > predicates between two components as edges; it may be any
+ * forest.  A tree T of components C_1..C_m counts as one component of P_T rows, the number of row
+ * tuples (r_1..r_m) satisfying every link of T; a select of a binding of C_x prints sum_i v_i *
+ * W_x(i) times the other components' sizes mod 2^64, where W_x(i) is the number of such tuples with
+ * r_x = i: W_x = prod_{y in N(x)} M_{y->x}, M_{y->x}(i) = sum_{j in C_y : kx_i op ky_j} U_{y\x}(j),
+ * U_{y\x} = prod_{z in N(y), z != x} M_{z->y} (1 for a leaf) -- e->theta_wsums, one call per
+ * message, the product taken through its `mul` (a component that needs several different products
+ * repeats a call per factor it cannot reuse).  The message y -> x is scheduled exactly when x's
+ * side of that edge holds a root: a component a select reads (the first one of the tree when none
+ * does).  At N ranks a message gathers C_y's keys and, unless y is a leaf toward x, U_{y\x}
+ * (e->allgather, rank order).  Messages are exact: a tree whose components' global sizes multiply to
+ * 2^64 or more is QE_ETOOBIG, as is a link side of 2^32 rows or more.  QE_ENOTSUP (decided on the
+ * text alone, qe_plan_why names the reason): a cycle of links, or two links between the same two
+ * components (a band).  A query whose components have at most one link each prints theta mode's
+ * line and row count.  QE_EINVAL: an engine without the theta callbacks, theta_wsums or
+ * checksums_weighted64. */
+int qe_plan_run_text_theta_tree(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows);
+int qe_plan_run_query_theta_tree(const qe_engine* e, void* query, void* out, uint64_t* rows);
 
 #ifdef __cplusplus
 }

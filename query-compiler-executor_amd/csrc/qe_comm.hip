@@ -1022,6 +1022,80 @@ int e_checksums_weighted(void* u, int n, const uint32_t* rels, const uint32_t* c
     });
 }
 
+// ---- theta-tree mode (include/qe_plan.h: the _theta_tree entry points alone read these two) ------
+// out[i] = mul[i] * sum_{j : qk[i] op sk[j]} sw[j]: both sides sorted with their positions (sk alone
+// when it carries no weights), one qe_theta_wsums pass whose gather reads each weight through its
+// key's position and whose store scatters each sum back to its key's position
+int e_theta_wsums(void* u, qe_h qk, qe_h sk, qe_h sw, char op, qe_h mul, qe_h* out, uint64_t* total) {
+    Eng* e = E(u);
+    return guard(e, [&] {
+        qe_ctx* c = e->c;
+        const DArr *q = A(qk), *s = A(sk), *wt = sw ? A(sw) : nullptr, *ml = mul ? A(mul) : nullptr;
+        if (op != '<' && op != '>') throw Error(QE_EINVAL, "theta_wsums: the operator is < or >");
+        if ((q->n >> 32) || (s->n >> 32)) throw Error(QE_ETOOBIG, "theta_wsums: a side of 2^32 keys or more");
+        if ((wt && (wt->n != s->n || !wt->u64)) || (ml && (ml->n != q->n || !ml->u64)))
+            throw Error(QE_EINVAL, "theta_wsums: weights aligned with their keys");
+        DBuf od(c, dalloc_t<uint64_t>(c, std::max<uint64_t>(q->n, 1)));
+        *total = 0;
+        if (q->n == 0 || s->n == 0) {          // nothing to compare with: every sum is 0
+            if (q->n) QE_HIP(hipMemsetAsync(od.p, 0, q->n * 8, c->stream));
+            *out = H(new_arr(c, od.release(), q->n, true));
+            return;
+        }
+        qe_pairs R = side_pairs(q, nullptr);   // (val null: the positions ride through the sort)
+        qe_pairs S{};
+        complete_keys(c, s);
+        void* skeys = nullptr;                 // S's sorted keys when a keys-only sort made a new buffer
+        try {
+            ck(qe_sort_pairs(c, &R), c);
+            if (wt) {                          // the weights are found through the positions
+                S = side_pairs(s, nullptr);
+                ck(qe_sort_pairs(c, &S), c);
+                pairs_need_keys(c, &S);
+                pairs_need_vals(c, &S);
+            } else {
+                const uint64_t sbits[2] = {s->kor, s->kand};
+                const SortOut so = radix_sort_u64(c, static_cast<const uint64_t*>(s->d), nullptr, s->n, false,
+                                                  s->bits ? sbits : nullptr);
+                if (so.keys_new) skeys = so.keys;
+                S.key = static_cast<uint64_t*>(so.keys);
+                S.n = s->n;
+                S.flags = QE_PAIRS_SORTED;
+            }
+            pairs_need_keys(c, &R);
+            pairs_need_vals(c, &R);
+            *total = theta_wsums(c, &R, &S, wt ? static_cast<const uint64_t*>(wt->d) : nullptr, s->n, op,
+                                 ml ? static_cast<const uint64_t*>(ml->d) : nullptr, static_cast<uint64_t*>(od.p),
+                                 q->n);
+        } catch (...) {
+            if (skeys) dfree(c, skeys);
+            if (wt) qe_pairs_free(c, &S);
+            qe_pairs_free(c, &R);
+            throw;
+        }
+        if (skeys) dfree(c, skeys);
+        if (wt) qe_pairs_free(c, &S);
+        qe_pairs_free(c, &R);
+        *out = H(new_arr(c, od.release(), q->n, true));
+    });
+}
+
+int e_checksums_weighted64(void* u, int n, const uint32_t* rels, const uint32_t* cols, const qe_h* rows, const qe_h* w,
+                           uint64_t* sums) {
+    Eng* e = E(u);
+    return guard(e, [&] {
+        qe_ctx* c = e->c;
+        for (int i = 0; i < n; i++) {
+            const DArr *r = A(rows[i]), *wt = A(w[i]);
+            if (rels[i] == QE_PLAN_VALUES || r->n != wt->n || !wt->u64)
+                throw Error(QE_EINVAL, "checksums_weighted64: rowids and 64-bit weights of one length");
+            const qe_list l = as_list(r);
+            ck(qe_checksum_weighted64(c, column(c, rels[i], cols[i]), &l, static_cast<const uint64_t*>(wt->d), &sums[i]),
+               c);
+        }
+    });
+}
+
 int e_length(void* u, qe_h h, uint64_t* n) {
     (void)u;
     *n = A(h)->n;
@@ -1293,6 +1367,8 @@ qe_engine make_engine(Eng* e) {
     g.allgather = e_allgather;
     g.theta_weights = e_theta_weights;
     g.checksums_weighted = e_checksums_weighted;
+    g.theta_wsums = e_theta_wsums;
+    g.checksums_weighted64 = e_checksums_weighted64;
     return g;
 }
 
@@ -1373,8 +1449,8 @@ int qe_comm_init_local(qe_ctx* const* ctxs, int nranks, qe_comm** out) {
     QE_API_END(c0)
 }
 
-// qe_run_queries_local (mode 0), qe_run_queries_relational_local (1) and qe_run_queries_theta_local (2)
-// over the same ranks
+// qe_run_queries_local (mode 0), qe_run_queries_relational_local (1), qe_run_queries_theta_local (2)
+// and qe_run_queries_theta_tree_local (3) over the same ranks
 static int run_local(qe_ctx* c, int nranks, int mode, const char* text, char** out, size_t* outlen,
                      uint64_t* refused, uint64_t* bytes_sent) {
     QE_API_BEGIN(c)
@@ -1399,7 +1475,8 @@ static int run_local(qe_ctx* c, int nranks, int mode, const char* text, char** o
         th.emplace_back([&, r] {
             qe_bind_thread(w[r]);
             const bool relational = mode != 0;
-            rcs[r] = mode == 2   ? qe_run_queries_theta(w[r], m[r], text, &outs[r], &lens[r])
+            rcs[r] = mode == 3   ? qe_run_queries_theta_tree(w[r], m[r], text, &outs[r], &lens[r])
+                     : mode == 2 ? qe_run_queries_theta(w[r], m[r], text, &outs[r], &lens[r])
                      : mode == 1 ? qe_run_queries_relational(w[r], m[r], text, &outs[r], &lens[r])
                                  : qe_run_queries_dist(w[r], m[r], text, &outs[r], &lens[r], &ref[r]);
             // never leave a peer waiting -- but the codes that end a relational batch are every rank's
@@ -1449,6 +1526,11 @@ int qe_run_queries_relational_local(qe_ctx* c, int nranks, const char* text, cha
 int qe_run_queries_theta_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen,
                                uint64_t* bytes_sent) {
     return run_local(c, nranks, 2, text, out, outlen, nullptr, bytes_sent);
+}
+
+int qe_run_queries_theta_tree_local(qe_ctx* c, int nranks, const char* text, char** out, size_t* outlen,
+                                    uint64_t* bytes_sent) {
+    return run_local(c, nranks, 3, text, out, outlen, nullptr, bytes_sent);
 }
 
 void qe_comm_fini(qe_comm* m) {
@@ -1653,6 +1735,26 @@ int qe_run_queries_theta(qe_ctx* c, qe_comm* m, const char* text, char** out, si
     uint64_t rows = c->last_result_rows;
     const int rc = qe_plan_run_text_theta(&g, text, out, outlen, &rows);
     if (rc != 0 && qe_plan_why()[0]) c->err = qe_plan_why();   // (a query refused before it ran)
+    c->last_result_rows = rows;
+    return rc;
+}
+
+int qe_run_queries_theta_tree(qe_ctx* c, qe_comm* m, const char* text, char** out, size_t* outlen) {
+    if (!c) return QE_EINVAL;
+    Eng e{c, m, m ? m->nranks : 1, m ? m->rank : 0, 0};
+    qe_engine g = make_engine(&e);
+    uint64_t rows = c->last_result_rows;
+    const int rc = qe_plan_run_text_theta_tree(&g, text, out, outlen, &rows);
+    if (rc != 0 && qe_plan_why()[0]) c->err = qe_plan_why();   // (a query refused before it ran)
+    c->last_result_rows = rows;
+    return rc;
+}
+
+int qe_plan_exec_query_theta_tree(qe_ctx* c, query_t* q, FILE* out) {
+    Eng e{c, nullptr, 1, 0, 0};
+    qe_engine g = make_engine(&e);
+    uint64_t rows = c->last_result_rows;
+    const int rc = qe_plan_run_query_theta_tree(&g, q, out, &rows);
     c->last_result_rows = rows;
     return rc;
 }

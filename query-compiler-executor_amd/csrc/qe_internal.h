@@ -337,6 +337,11 @@ void pairs_need_keys(qe_ctx* c, const qe_pairs* p);
 // theta mode (qe_join.hip): R->match[i] = #{j : R.key[i] op S.key[j]} (op '<' or '>', both sides
 // sorted and below 2^32 keys), scattered to w[R.val[i]] (w nullable, wn entries); returns the sum
 uint64_t theta_counts(qe_ctx* c, qe_pairs* R, const qe_pairs* S, char op, uint32_t* w, uint64_t wn);
+// theta-tree mode (qe_join.hip): out[R.val[i]] = (mul ? mul[R.val[i]] : 1) * sum_{j : R.key[i] op
+// S.key[j]} sw[S.val[j]] mod 2^64 (sw null: ones; nw weights, on outputs; the same preconditions);
+// returns the sum of out
+uint64_t theta_wsums(qe_ctx* c, const qe_pairs* R, const qe_pairs* S, const uint64_t* sw, uint64_t nw, char op,
+                     const uint64_t* mul, uint64_t* out, uint64_t on);
 void pairs_need_vals(qe_ctx* c, const qe_pairs* p);
 // (also drops a gathered histogram; keep_k32: a key buffer the pairs only borrow keeps its u32
 // keys, PreHist::k32, for another sort of it -- its owner's release frees them)

@@ -1056,6 +1056,24 @@ void qe_counts_free(qe_ctx* c, uint32_t* d) {
     if (c) dfree(c, d);
 }
 
+int qe_u64_from_host(qe_ctx* c, const uint64_t* h, uint64_t n, uint64_t** d) {
+    QE_API_BEGIN(c)
+    if (!d || (n && !h)) throw Error(QE_EINVAL, "qe_u64_from_host: bad arguments");
+    *d = dalloc_t<uint64_t>(c, std::max<uint64_t>(n, 1));
+    if (n) QE_HIP(hipMemcpyAsync(*d, h, n * 8, hipMemcpyHostToDevice, c->stream));
+    QE_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+    QE_API_END(c)
+}
+
+int qe_u64_to_host(qe_ctx* c, const uint64_t* d, uint64_t n, uint64_t* h) {
+    QE_API_BEGIN(c)
+    if (n) QE_HIP(hipMemcpyAsync(h, d, n * 8, hipMemcpyDeviceToHost, c->stream));
+    QE_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+    QE_API_END(c)
+}
+
 int qe_counts_to_host(qe_ctx* c, const uint32_t* d, uint64_t n, uint32_t* h) {
     QE_API_BEGIN(c)
     if (n) QE_HIP(hipMemcpyAsync(h, d, n * 4, hipMemcpyDeviceToHost, c->stream));

@@ -728,7 +728,8 @@ typedef struct {
     atomic_int* stop;          /* the first query index known to end the batch (+1), 0 none */
     int plan;                  /* QE_EXEC_PLAN: the partitioned plan, faithful fallback */
     int relational;            /* QE_EXEC_RELATIONAL: the plan's relational mode, no fallback */
-    int theta;                 /* QE_EXEC_THETA: the relational mode with column </> column honoured */
+    int theta;                 /* QE_EXEC_THETA: the relational mode with column </> column honoured;
+                                * 2, QE_EXEC_THETA_TREE: with any forest of such links */
 } lane_t;
 
 static void* lane_main(void* arg) {
@@ -747,7 +748,8 @@ static void* lane_main(void* arg) {
             L->rcs[i] = QE_ENOMEM;
         } else {
             if (!L->relational) qe_arrange_predicates(&L->qs[i]);
-            L->rcs[i] = L->theta      ? qe_plan_exec_query_theta(L->ctx, &L->qs[i], f)
+            L->rcs[i] = L->theta == 2 ? qe_plan_exec_query_theta_tree(L->ctx, &L->qs[i], f)
+                        : L->theta    ? qe_plan_exec_query_theta(L->ctx, &L->qs[i], f)
                         : L->relational ? qe_plan_exec_query_relational(L->ctx, &L->qs[i], f)
                         : L->plan     ? qe_plan_exec_query(L->ctx, &L->qs[i], f)
                                       : qe_exec_query(L->ctx, &L->qs[i], f);
@@ -770,9 +772,9 @@ int qe_run_queries_lanes(qe_ctx* ctx, int workers, int executor, const char* tex
     *out = NULL;
     *outlen = 0;
     if (executor != QE_EXEC_FAITHFUL && executor != QE_EXEC_PLAN && executor != QE_EXEC_RELATIONAL &&
-        executor != QE_EXEC_THETA)
+        executor != QE_EXEC_THETA && executor != QE_EXEC_THETA_TREE)
         return QE_EINVAL;
-    const int theta = executor == QE_EXEC_THETA;
+    const int theta = executor == QE_EXEC_THETA_TREE ? 2 : executor == QE_EXEC_THETA;
     const int relational = executor == QE_EXEC_RELATIONAL || theta;   /* (no arranging, no fallback) */
     const int plan = executor == QE_EXEC_PLAN || relational;   /* (the plan's engine, its shared sorts) */
     if (workers <= 1) {
@@ -780,7 +782,8 @@ int qe_run_queries_lanes(qe_ctx* ctx, int workers, int executor, const char* tex
         uint64_t refused = 0;
         int rc = qe_sort_cache(ctx, 1);          /* the batch's base-column sorts, shared */
         if (rc == 0)
-            rc = theta      ? qe_run_queries_theta(ctx, NULL, text, out, outlen)
+            rc = theta == 2 ? qe_run_queries_theta_tree(ctx, NULL, text, out, outlen)
+                 : theta    ? qe_run_queries_theta(ctx, NULL, text, out, outlen)
                  : relational ? qe_run_queries_relational(ctx, NULL, text, out, outlen)
                             : qe_run_queries_dist(ctx, NULL, text, out, outlen, &refused);
         const int rc2 = qe_sort_cache(ctx, 0);

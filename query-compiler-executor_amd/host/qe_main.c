@@ -26,6 +26,9 @@
  *                 answer ends the batch: the lines of the queries before it, then EXIT_LIBQE.
  *   QE_RELATIONAL=2  theta mode: the relational mode with a written column < / > column predicate
  *                 honoured instead of refused, in the same launch forms
+ *   QE_RELATIONAL=3  theta-tree mode: theta mode with chains and trees of such predicates between
+ *                 components, in the same launch forms; a cycle or a band of
+ *                 them ends the batch like any query the mode cannot answer (EXIT_LIBQE)
  *
  * Exit status: 0; 1 where the reference calls exit(EXIT_FAILURE); EXIT_LIBQE (70, sysexits'
  * EX_SOFTWARE) when libqe reports an error (a message on stderr); a rank of QE_GPUS=N killed by
@@ -172,8 +175,9 @@ static int run_rank(const input_t* in, int rank, int world, int* to_peers, int f
     char* out = NULL;
     size_t outlen = 0;
     uint64_t refused = 0;
-    const int relational = env_int("QE_RELATIONAL", 0, 0, 2);
-    int rc = relational == 2   ? qe_run_queries_theta(c, m, in->text, &out, &outlen)
+    const int relational = env_int("QE_RELATIONAL", 0, 0, 3);
+    int rc = relational == 3   ? qe_run_queries_theta_tree(c, m, in->text, &out, &outlen)
+             : relational == 2 ? qe_run_queries_theta(c, m, in->text, &out, &outlen)
              : relational == 1 ? qe_run_queries_relational(c, m, in->text, &out, &outlen)
                                : qe_run_queries_dist(c, m, in->text, &out, &outlen, &refused);
     int status = finish(rc, out, outlen, rank == 0);
@@ -280,15 +284,17 @@ int main(void) {
     size_t outlen = 0;
     const int plan = env_int("QE_PLAN", 1, 0, 1);
     const int lranks = env_int("QE_LOCAL_RANKS", 0, 0, 16);
-    const int relational = env_int("QE_RELATIONAL", 0, 0, 2);
+    const int relational = env_int("QE_RELATIONAL", 0, 0, 3);
     int rc;
     if (lranks >= 2) {
         uint64_t refused = 0, sent = 0;
-        rc = relational == 2   ? qe_run_queries_theta_local(c, lranks, in.text, &out, &outlen, &sent)
+        rc = relational == 3   ? qe_run_queries_theta_tree_local(c, lranks, in.text, &out, &outlen, &sent)
+             : relational == 2 ? qe_run_queries_theta_local(c, lranks, in.text, &out, &outlen, &sent)
              : relational == 1 ? qe_run_queries_relational_local(c, lranks, in.text, &out, &outlen, &sent)
                                : qe_run_queries_local(c, lranks, in.text, &out, &outlen, &refused, &sent);
     } else {
-        const int executor = relational == 2   ? QE_EXEC_THETA
+        const int executor = relational == 3   ? QE_EXEC_THETA_TREE
+                             : relational == 2 ? QE_EXEC_THETA
                              : relational == 1 ? QE_EXEC_RELATIONAL
                              : plan            ? QE_EXEC_PLAN
                                                : QE_EXEC_FAITHFUL;

@@ -1192,11 +1192,46 @@ static int theta_validate(const query_t* q) {
     return rc;
 }
 
+/* theta-tree mode: the links (as above) are the edges of a graph over the components; any forest is
+ * accepted.  Two links between one pair of components (a band) and a longer cycle are not */
+static int tree_validate(const query_t* q) {
+    int* root = rel_eq_roots(q);
+    int* tree = (int*)malloc((q->nrels + 1) * sizeof(int));
+    int* ea = (int*)malloc((q->npreds + 1) * sizeof(int));
+    int* eb = (int*)malloc((q->npreds + 1) * sizeof(int));
+    for (size_t i = 0; i <= q->nrels; i++) tree[i] = (int)i;
+    int rc = 0, ne = 0;
+    for (size_t i = 0; rc == 0 && i < q->npreds; i++) {
+        const pred_t* p = &q->preds[i];
+        if (p->type != 0 || p->op == '=') continue;
+        const int a = root[p->frel], b = root[p->srel];
+        if (a == b) continue;                                /* a filter or an in-component selection */
+        int band = 0;
+        for (int k = 0; k < ne; k++) band |= (ea[k] == a && eb[k] == b) || (ea[k] == b && eb[k] == a);
+        if (band)
+            rc = refuse("two column </> column predicates between the same two unconnected components (a band)");
+        else if (uf_find(tree, a) == uf_find(tree, b))
+            rc = refuse("a cycle of column </> column links between components");
+        else
+            tree[uf_find(tree, a)] = uf_find(tree, b);
+        ea[ne] = a;
+        eb[ne++] = b;
+    }
+    free(root);
+    free(tree);
+    free(ea);
+    free(eb);
+    return rc;
+}
+
+/* theta: 0 the relational mode, 1 theta mode, 2 theta-tree mode */
 static int rel_validate(const qe_engine* e, const query_t* q, int theta) {
     g_why[0] = 0;
     if (!e->select_eq) return refuse("the engine has no select_eq"), QE_EINVAL;
     if (theta && !(e->select_cmp && e->allgather && e->theta_weights && e->checksums_weighted))
         return refuse("the engine lacks a theta callback"), QE_EINVAL;
+    if (theta == 2 && !(e->theta_wsums && e->checksums_weighted64))
+        return refuse("the engine lacks a theta-tree callback"), QE_EINVAL;
     if (!s_query_valid(e, q)) return refuse("out-of-range relation / column / binding"), QE_EINVAL;
     if (q->nsel == 0) return refuse("no select"), QE_EINVAL;
     if (q->nrels > 60) return refuse("more than 60 bindings"), QE_EINVAL;   /* (side_t's carried bindings) */
@@ -1206,7 +1241,7 @@ static int rel_validate(const qe_engine* e, const query_t* q, int theta) {
         if (p->type == 0 && p->op != '=' && !theta)   /* (the reference joins on equality whatever is written) */
             return refuse("column %c column is not an equi-join", p->op);
     }
-    return theta ? theta_validate(q) : 0;
+    return theta == 2 ? tree_validate(q) : theta ? theta_validate(q) : 0;
 }
 
 /* does some column = column predicate of q run inside a component, whatever the join order?  A
@@ -1376,6 +1411,203 @@ static int rel_link(plan_t* P, const pred_t* p, link_t* L) {
     return rc;
 }
 
+/* ---- theta-tree mode: a forest of links (qe_plan.h) -------------------------------- */
+/* a link as an edge: components c[0] (the predicate's left side) and c[1], key bindings and columns,
+ * k[t] this rank's keys of side t, all[t] every rank's (world > 1); both made when first needed */
+typedef struct { int c[2], b[2], col[2]; char op; qe_h k[2], all[2]; } tedge_t;
+/* a product of messages into component `node` over the edges of `mask`: a uint64 list aligned with
+ * this rank's rows of the component, `total` its sum (this rank's share), `gathered` every rank's */
+typedef struct { int node; uint64_t mask; qe_h h, gathered; uint64_t total; } tprod_t;
+typedef struct {
+    plan_t* P;
+    int ne, np, calls;
+    tedge_t* E;
+    tprod_t* prod;
+    uint64_t* adj;                                           /* per component: its edges, as a mask */
+    uint8_t* isroot;                                         /* per component: a root of its tree */
+} trees_t;
+
+/* does z's side of edge ei hold a root? */
+static int tree_side_has_root(const trees_t* T, int z, int ei) {
+    if (T->isroot[z]) return 1;
+    for (int ej = 0; ej < T->ne; ej++)
+        if (ej != ei && (T->adj[z] >> ej & 1) &&
+            tree_side_has_root(T, T->E[ej].c[T->E[ej].c[0] == z ? 1 : 0], ej))
+            return 1;
+    return 0;
+}
+
+static int tree_keys(trees_t* T, int ei, int t, int gathered, qe_h* out) {
+    plan_t* P = T->P;
+    const qe_engine* e = P->e;
+    tedge_t* g = &T->E[ei];
+    if (g->k[t] == NONE) {
+        comp_t* c = &P->C[g->c[t]];
+        member* m = &c->m[member_idx(c, g->b[t])];
+        if (m->vcol) return P->rc = QE_EINVAL;               /* (a reader of rowids that the hints missed) */
+        ECHK(rows_of(P, m));
+        ECHK(e->keys(e->u, P->q->rels[g->b[t]], (uint32_t)g->col[t], m->rows, &g->k[t]));
+    }
+    if (gathered && e->world > 1 && g->all[t] == NONE) ECHK(e->allgather(e->u, g->k[t], &g->all[t]));
+    *out = gathered && e->world > 1 ? g->all[t] : g->k[t];
+    return 0;
+}
+
+/* the product over `mask` (edges at y) of the messages into y; *pi its entry, -1 for the empty
+ * product (all ones).  Continues the largest product of a subset already made, one theta_wsums call
+ * per edge still missing: the message z -> y, its far weights U_{z\y} the product at z over z's
+ * other edges, multiplied into what is there through `mul`.  Edges that lead to a root come last:
+ * the product without such an edge is what the message along it needs, and is met on the way */
+static int tree_product(trees_t* T, int y, uint64_t mask, int* pi) {
+    plan_t* P = T->P;
+    const qe_engine* e = P->e;
+    *pi = -1;
+    if (!mask) return 0;
+    uint64_t have = 0;
+    for (int i = 0; i < T->np; i++) {
+        const tprod_t* r = &T->prod[i];
+        if (r->node != y || (r->mask & ~mask)) continue;
+        if (*pi < 0 || __builtin_popcountll(r->mask) > __builtin_popcountll(have)) {
+            *pi = i;
+            have = r->mask;
+        }
+    }
+    const uint64_t missing = mask & ~have;
+    for (int k = 0; k < 2 * T->ne; k++) {
+        const int ei = k % T->ne;
+        if (!(missing >> ei & 1)) continue;
+        tedge_t* g = &T->E[ei];
+        const int ty = g->c[0] == y ? 0 : 1, z = g->c[!ty];
+        if (tree_side_has_root(T, z, ei) != (k >= T->ne)) continue;
+        int zi = -1;
+        ECHK(tree_product(T, z, T->adj[z] & ~(1ull << ei), &zi));
+        qe_h qk = NONE, sk = NONE, sw = NONE;
+        ECHK(tree_keys(T, ei, ty, 0, &qk));
+        ECHK(tree_keys(T, ei, !ty, 1, &sk));
+        if (zi >= 0) {
+            tprod_t* r = &T->prod[zi];
+            if (e->world > 1 && r->gathered == NONE) ECHK(e->allgather(e->u, r->h, &r->gathered));
+            sw = e->world > 1 ? r->gathered : r->h;
+        }
+        tprod_t* n = &T->prod[T->np];
+        n->node = y;
+        n->mask = have | 1ull << ei;
+        n->h = n->gathered = NONE;
+        ECHK(e->theta_wsums(e->u, qk, sk, sw, ty ? flip_op(g->op) : g->op, *pi >= 0 ? T->prod[*pi].h : NONE, &n->h,
+                            &n->total));
+        T->calls++;
+        have = n->mask;
+        *pi = T->np++;
+    }
+    return 0;
+}
+
+static void trees_free(trees_t* T) {
+    for (int i = 0; i < T->np; i++) {
+        rel(T->P, T->prod[i].h);
+        rel(T->P, T->prod[i].gathered);
+    }
+    for (int i = 0; i < T->ne; i++)
+        for (int t = 0; t < 2; t++) {
+            rel(T->P, T->E[i].k[t]);
+            rel(T->P, T->E[i].all[t]);
+        }
+    free(T->E);
+    free(T->prod);
+    free(T->adj);
+    free(T->isroot);
+}
+
+/* the pending < / > predicates as a forest over the components: grp_of[c] = c's tree (numbered from
+ * 0; -1 for a component no link touches), lead[t] the tree's first component, share[t] this rank's
+ * share of P_t, wcomp[c] the weights W_c of every component a select reads.  Returns the trees' count
+ * in *ntrees.  Every rank makes the same calls: the schedule follows from the text alone. */
+static int rel_trees(plan_t* P, const int* pending, size_t np, trees_t* T, int* grp_of, int* lead, uint64_t* share,
+                     qe_h* wcomp, int* ntrees) {
+    const query_t* q = P->q;
+    memset(T, 0, sizeof *T);
+    T->P = P;
+    T->E = (tedge_t*)calloc(np + 1, sizeof(tedge_t));
+    T->adj = (uint64_t*)calloc((size_t)P->nc + 1, sizeof(uint64_t));
+    *ntrees = 0;
+    if (np > 63) return P->rc = QE_EINVAL;                   /* (a forest over at most 60 bindings has fewer) */
+    size_t deg = 0;
+    for (size_t i = 0; i < np; i++) {
+        const pred_t* p = &q->preds[pending[i]];
+        tedge_t* g = &T->E[T->ne];
+        g->c[0] = P->comp_of[p->frel];
+        g->c[1] = P->comp_of[p->srel];
+        g->b[0] = (int)p->frel;
+        g->b[1] = (int)p->srel;
+        g->col[0] = (int)p->fcol;
+        g->col[1] = (int)p->scol;
+        g->op = p->op;
+        for (int t = 0; t < 2; t++) {
+            if (P->C[g->c[t]].size >> 32) {                  /* global sizes: every rank leaves here */
+                P->rc = QE_ETOOBIG;
+                return refuse("a column %c column link side of 2^32 rows or more", p->op), QE_ETOOBIG;
+            }
+            T->adj[g->c[t]] |= 1ull << T->ne;
+            deg++;
+        }
+        T->ne++;
+    }
+    /* every product made is a new prefix of some component's edges: at most one per (root, edge
+     * end) -- bounded by roots * edge ends */
+    T->prod = (tprod_t*)calloc((deg + 1) * ((size_t)P->nc + 1), sizeof(tprod_t));
+    /* the trees: flood from each linked component in index order, so a tree's lead is its first one */
+    for (int c0 = 0; c0 < P->nc; c0++) {
+        if (!P->C[c0].alive || !T->adj[c0] || grp_of[c0] >= 0) continue;
+        const int t = (*ntrees)++;
+        lead[t] = c0;
+        grp_of[c0] = t;
+        uint64_t bound = 1;
+        int big = 0;
+        for (int again = 1; again;) {
+            again = 0;
+            for (int i = 0; i < T->ne; i++) {
+                const int a = T->E[i].c[0], b = T->E[i].c[1];
+                if ((grp_of[a] == t) != (grp_of[b] == t)) {
+                    grp_of[a] = grp_of[b] = t;
+                    again = 1;
+                }
+            }
+        }
+        /* messages must be exact (NULL is decided by P_t == 0): none exceeds the product of the sizes */
+        for (int c = 0; c < P->nc; c++)
+            if (grp_of[c] == t && __builtin_mul_overflow(bound, P->C[c].size, &bound)) big = 1;
+        if (big) {
+            P->rc = QE_ETOOBIG;
+            return refuse("a tree of column </> column links whose components' sizes multiply to 2^64 or more"),
+                   QE_ETOOBIG;
+        }
+    }
+    /* the roots: the components the selects read; a tree none reads is rooted at its lead, for P_t */
+    uint8_t* read = (uint8_t*)calloc((size_t)P->nc + 1, 1);
+    uint8_t* any = (uint8_t*)calloc((size_t)*ntrees + 1, 1);
+    for (size_t s = 0; s < q->nsel; s++) {
+        const int c = P->comp_of[q->sel[2 * s]];
+        if (c >= 0 && P->C[c].alive && grp_of[c] >= 0) read[c] = any[grp_of[c]] = 1;
+    }
+    T->isroot = (uint8_t*)calloc((size_t)P->nc + 1, 1);
+    for (int c = 0; c < P->nc; c++)
+        T->isroot[c] = grp_of[c] >= 0 && (read[c] || (!any[grp_of[c]] && lead[grp_of[c]] == c));
+    int rc = 0;
+    for (int c = 0; rc == 0 && c < P->nc; c++) {
+        if (!T->isroot[c]) continue;
+        int pi = -1;
+        rc = tree_product(T, c, T->adj[c], &pi);
+        if (rc) break;
+        wcomp[c] = T->prod[pi].h;
+        if (!(any[grp_of[c]] & 2)) share[grp_of[c]] = T->prod[pi].total;   /* (sum W is P_t at every root) */
+        any[grp_of[c]] |= 2;
+    }
+    free(read);
+    free(any);
+    if (rc && !P->rc) P->rc = rc;
+    return rc;
+}
+
 static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint64_t* rows_out, int theta) {
     int rc = rel_validate(e, q, theta);
     if (rc) return rc;
@@ -1457,13 +1689,31 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
     for (size_t b = 0; rc == 0 && !zero && b < q->nrels; b++)
         if (P->comp_of[b] < 0) (void)component(P, (int)b);
     /* theta mode: what is still pending links two components (rel_validate: at most one link each) */
+    /* a group: the components that count as one -- a linked pair, or (theta-tree mode) a tree of links.
+     * link_of[c] = c's group or -1, lead[g] the component the group is counted with, gP[g] its size
+     * (this rank's share until the all-reduce), wcomp[c] the weights of c's rows where a select needs
+     * them (uint32 lists in theta mode, uint64 in theta-tree mode) */
+    const size_t ncmax = 2 * nb + q->npreds + 1;
     link_t* links = (link_t*)calloc(np + 1, sizeof(link_t));
-    int* link_of = (int*)malloc((2 * nb + q->npreds + 1) * sizeof(int));
-    for (size_t i = 0; i < 2 * nb + q->npreds + 1; i++) link_of[i] = -1;
+    int* link_of = (int*)malloc(ncmax * sizeof(int));
+    int* lead = (int*)calloc(ncmax, sizeof(int));
+    uint64_t* gP = (uint64_t*)calloc(ncmax, sizeof(uint64_t));
+    qe_h* wcomp = (qe_h*)calloc(ncmax, sizeof(qe_h));
+    for (size_t i = 0; i < ncmax; i++) link_of[i] = -1;
     int nl = 0;
-    for (size_t i = 0; rc == 0 && !zero && i < np; i++) {
+    trees_t TT;
+    int have_trees = 0;
+    if (theta == 2 && rc == 0 && !zero && np) {
+        have_trees = 1;
+        rc = rel_trees(P, pending, np, &TT, link_of, lead, gP, wcomp, &nl);
+    }
+    for (size_t i = 0; theta != 2 && rc == 0 && !zero && i < np; i++) {
         rc = rel_link(P, &q->preds[pending[i]], &links[nl]);
         link_of[links[nl].A] = link_of[links[nl].B] = nl;
+        lead[nl] = links[nl].A;
+        gP[nl] = links[nl].P;
+        wcomp[links[nl].A] = links[nl].wA;
+        wcomp[links[nl].B] = links[nl].wB;
         nl++;
     }
     /* the selects' sums: a select prints its component's sum times the other components' sizes, mod
@@ -1494,21 +1744,22 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
             srel[ns] = mb->vcol ? QE_PLAN_VALUES : q->rels[b];
             scol[ns] = (uint32_t)q->sel[2 * s + 1];
             srows[ns] = mb->rows;
-            if (w) sw[ns] = links[link_of[ci]].A == ci ? links[link_of[ci]].wA : links[link_of[ci]].wB;
+            if (w) sw[ns] = wcomp[ci];
             at[ns++] = (int)s;
         }
         if (rc == 0 && ns) {
             uint64_t* part = (uint64_t*)calloc((size_t)ns, sizeof(uint64_t));
-            rc = w ? e->checksums_weighted(e->u, ns, srel, scol, srows, sw, part)
-                   : e->checksums(e->u, ns, srel, scol, srows, part);
+            rc = !w           ? e->checksums(e->u, ns, srel, scol, srows, part)
+                 : theta == 2 ? e->checksums_weighted64(e->u, ns, srel, scol, srows, sw, part)
+                              : e->checksums_weighted(e->u, ns, srel, scol, srows, sw, part);
             for (int k = 0; k < ns; k++) sums[at[k]] = part[k];
             free(part);
         }
     }
     /* one all-reduce: the sums and, behind them, every link's pair share */
-    for (int l = 0; l < nl; l++) sums[q->nsel + (size_t)l] = links[l].P;
+    for (int l = 0; l < nl; l++) sums[q->nsel + (size_t)l] = gP[l];
     if (rc == 0 && !zero && e->world > 1) rc = e->allreduce(e->u, sums, (int)q->nsel + nl);
-    for (int l = 0; l < nl; l++) links[l].P = sums[q->nsel + (size_t)l];
+    for (int l = 0; l < nl; l++) gP[l] = sums[q->nsel + (size_t)l];
     /* total = the product of the component sizes (the aggregate last join's pair count is one, and so
      * is a linked pair's P) */
     uint64_t total = 1;
@@ -1516,8 +1767,8 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
         int sat = 0;
         for (int i = -1; i < P->nc; i++) {
             if (i < 0 ? !P->agg : !P->C[i].alive) continue;
-            if (i >= 0 && link_of[i] >= 0 && links[link_of[i]].B == i) continue;   /* (counted with its A) */
-            const uint64_t sz = i < 0 ? P->agg_size : link_of[i] >= 0 ? links[link_of[i]].P : P->C[i].size;
+            if (i >= 0 && link_of[i] >= 0 && lead[link_of[i]] != i) continue;   /* (counted with its group's lead) */
+            const uint64_t sz = i < 0 ? P->agg_size : link_of[i] >= 0 ? gP[link_of[i]] : P->C[i].size;
             if (sz == 0) zero = 1;
             if (__builtin_mul_overflow(total, sz, &total)) sat = 1;
         }
@@ -1530,8 +1781,8 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
         uint64_t m = 1;
         for (int i = -1; i < P->nc; i++) {
             if (i == ci || (i < 0 ? !P->agg : !P->C[i].alive)) continue;
-            if (i >= 0 && link_of[i] >= 0 && (link_of[i] == li || links[link_of[i]].B == i)) continue;
-            m *= i < 0 ? P->agg_size : link_of[i] >= 0 ? links[link_of[i]].P : P->C[i].size;
+            if (i >= 0 && link_of[i] >= 0 && (link_of[i] == li || lead[link_of[i]] != i)) continue;
+            m *= i < 0 ? P->agg_size : link_of[i] >= 0 ? gP[link_of[i]] : P->C[i].size;
         }
         mult[s] = m;
     }
@@ -1543,12 +1794,16 @@ static int plan_query_rel(const qe_engine* e, const query_t* q, FILE* out, uint6
         fputc('\n', out);
         if (rows_out) *rows_out = total;
     }
-    for (int l = 0; l < nl; l++) {
+    for (int l = 0; theta != 2 && l < nl; l++) {
         rel(P, links[l].wA);
         rel(P, links[l].wB);
     }
+    if (have_trees) trees_free(&TT);
     free(links);
     free(link_of);
+    free(lead);
+    free(gP);
+    free(wcomp);
     free(sums);
     free(mult);
     free(srel);
@@ -1691,4 +1946,12 @@ int qe_plan_run_query_theta(const qe_engine* e, void* query, void* out, uint64_t
 
 int qe_plan_run_text_theta(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows) {
     return run_text_rel(e, text, out, outlen, rows, 1);
+}
+
+int qe_plan_run_query_theta_tree(const qe_engine* e, void* query, void* out, uint64_t* rows) {
+    return run_query_rel(e, query, out, rows, 2);
+}
+
+int qe_plan_run_text_theta_tree(const qe_engine* e, const char* text, char** out, size_t* outlen, uint64_t* rows) {
+    return run_text_rel(e, text, out, outlen, rows, 2);
 }

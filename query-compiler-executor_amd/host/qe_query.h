@@ -76,6 +76,8 @@ int qe_plan_exec_query_relational(struct qe_ctx* ctx, query_t* q, FILE* out);
 /* csrc/qe_comm.hip: the same through the plan's theta mode (a written column < / > column predicate
  * honoured) */
 int qe_plan_exec_query_theta(struct qe_ctx* ctx, query_t* q, FILE* out);
+/* csrc/qe_comm.hip: the same through the plan's theta-tree mode (any forest of such links) */
+int qe_plan_exec_query_theta_tree(struct qe_ctx* ctx, query_t* q, FILE* out);
 
 #ifdef __cplusplus
 }

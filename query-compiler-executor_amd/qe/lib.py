@@ -17,6 +17,7 @@ HEADER = os.path.join(os.path.dirname(PKG), "include", "qe.h")
 
 QE_EINVAL, QE_EHIP, QE_ENOMEM, QE_EEXIT, QE_ETOOBIG, QE_ENOTSUP = -1, -2, -3, -4, -5, -6
 QE_EXEC_FAITHFUL, QE_EXEC_PLAN, QE_EXEC_RELATIONAL, QE_EXEC_THETA = 0, 1, 2, 3   # qe_run_queries_lanes' executors
+QE_EXEC_THETA_TREE = 4
 LIST_DISTINCT = 1
 PAIRS_DISTINCT, PAIRS_SORTED = 1, 2
 PAIRS_MATCHED = 8
@@ -157,6 +158,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "qe_run_queries_theta": (I, [P, P, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
         "qe_run_queries_theta_local": (I, [P, I, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_uint64)]),
+        "qe_theta_wsums": (I, [P, C.POINTER(Pairs), C.POINTER(Pairs), P, C.c_char, P, P, C.POINTER(C.c_uint64)]),
+        "qe_checksum_weighted64": (I, [P, Col, C.POINTER(List), P, C.POINTER(C.c_uint64)]),
+        "qe_u64_from_host": (I, [P, P, C.c_uint64, C.POINTER(C.c_void_p)]),
+        "qe_u64_to_host": (I, [P, P, C.c_uint64, P]),
+        "qe_run_queries_theta_tree": (I, [P, P, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+        "qe_run_queries_theta_tree_local": (I, [P, I, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_uint64)]),
         "qe_bind_thread": (I, [P]),
     }
     for name, (res, args) in sig.items():
@@ -274,7 +282,7 @@ class Ctx:
         s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
         if out.value:
             self.lib.qe_free_host(out)
-        if executor in (QE_EXEC_RELATIONAL, QE_EXEC_THETA):
+        if executor in (QE_EXEC_RELATIONAL, QE_EXEC_THETA, QE_EXEC_THETA_TREE):
             return s, self._relational_code(rc)
         if rc not in (0, QE_EEXIT):
             raise QEError(rc, self.lib.qe_last_error(self.h).decode())
@@ -327,6 +335,28 @@ class Ctx:
         out, n, sent = C.c_void_p(), C.c_size_t(), C.c_uint64()
         rc = self.lib.qe_run_queries_theta_local(self.h, nranks, text.encode(), C.byref(out), C.byref(n),
                                                  C.byref(sent))
+        s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
+        if out.value:
+            self.lib.qe_free_host(out)
+        return s, self._relational_code(rc), sent.value
+
+    def run_theta_tree(self, text: str, comm: "Comm | None" = None) -> tuple[str, int]:
+        """qe_run_queries_theta_tree: run_theta with any forest of column < / > column links between
+        components (chains, stars, trees) -> (stdout on rank 0, 0 or the code that ended the batch)"""
+        out, n = C.c_void_p(), C.c_size_t()
+        rc = self.lib.qe_run_queries_theta_tree(self.h, comm.h if comm else None, text.encode(), C.byref(out),
+                                                C.byref(n))
+        s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
+        if out.value:
+            self.lib.qe_free_host(out)
+        return s, self._relational_code(rc)
+
+    def run_theta_tree_local(self, text: str, nranks: int) -> tuple[str, int, int]:
+        """qe_run_queries_theta_tree_local: the same on `nranks` in-process ranks of this GPU ->
+        (stdout, 0 or the code that ended the batch, bytes exchanged)"""
+        out, n, sent = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        rc = self.lib.qe_run_queries_theta_tree_local(self.h, nranks, text.encode(), C.byref(out), C.byref(n),
+                                                      C.byref(sent))
         s = C.string_at(out, n.value).decode("latin-1") if out.value else ""
         if out.value:
             self.lib.qe_free_host(out)
@@ -446,6 +476,33 @@ class Ctx:
         pairs = C.c_uint64()
         self._chk(self.lib.qe_theta_counts(self.h, C.byref(R), C.byref(S), op.encode(), C.byref(pairs)))
         return pairs.value
+
+    def u64_from_host(self, a: np.ndarray) -> int:
+        """a device array of uint64 words (free with buffer_free) -> its pointer"""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        d = C.c_void_p()
+        self._chk(self.lib.qe_u64_from_host(self.h, a.ctypes.data, len(a), C.byref(d)))
+        return d.value
+
+    def u64_to_host(self, ptr: int, n: int) -> np.ndarray:
+        a = np.empty(n, dtype=np.uint64)
+        self._chk(self.lib.qe_u64_to_host(self.h, ptr, n, a.ctypes.data))
+        return a
+
+    def theta_wsums(self, R: Pairs, S: Pairs, sw: int | None, op: str, mul: int | None, out: int) -> int:
+        """qe_theta_wsums: out[R.val[i]] = (mul ? mul[R.val[i]] : 1) * sum_{j : R.key[i] op S.key[j]}
+        sw[S.val[j]] mod 2^64 for two sorted sides (sw, mul, out: device uint64 pointers; sw None:
+        ones) -> the sum of out"""
+        total = C.c_uint64()
+        self._chk(self.lib.qe_theta_wsums(self.h, C.byref(R), C.byref(S), sw, op.encode(), mul, out, C.byref(total)))
+        return total.value
+
+    def checksum_weighted64(self, col: Col, rows: List | None, w: int) -> int:
+        """qe_checksum_weighted64: sum of col[rows[i]] * w[i] mod 2^64, w a device uint64 pointer"""
+        s = C.c_uint64()
+        self._chk(self.lib.qe_checksum_weighted64(self.h, col, C.byref(rows) if rows is not None else None, w,
+                                                  C.byref(s)))
+        return s.value
 
     def select_equal_tile(self) -> int:
         return int(self.lib.qe_select_equal_tile())
